@@ -3,7 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--groups G] [--slots P] [--workload 2|3|5]
                     [--fuse T] [--split S] [--variant 0|2|4|5] [--publish-every E] [--one-engine] [--no-cpu-baseline]
-                    [--inflights CAP] [--no-extras] [--c5-variant V]
+                    [--inflights CAP] [--no-extras] [--c5-variant V] [--dump-outputs DIR]
 
 The default (N = 1) line also carries, as sub-objects with their own `roofline` (each labelled with its memory regime):
 `recompute_only` (+ `_out_of_cache`), `out_of_cache`, `between_regimes` (2.4 M groups), `other_configs` (every other BASELINE configuration that fits one
@@ -766,6 +766,28 @@ def self_launch(n):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_LIMIT = 64 << 20  # bytes of all the .npy payloads --dump-outputs writes
+DUMP_SAMPLE_SEED = 0x0D0D  # which groups a sample keeps when the whole output would not fit DUMP_LIMIT
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: every per-group array of `arrays` (name -> 1-D or [ranks][groups] array, the same group count
+    along the last axis) as DIR/<name>.npy in float64 (exact for integers below 2**53). When the whole would exceed
+    DUMP_LIMIT bytes, the same fixed, seeded sample of groups is taken from every array, and DIR/group_index.npy holds
+    the sampled group numbers (ascending)."""
+    n = next(iter(arrays.values())).shape[-1]
+    per_group = sum(8 * (a.size // n) for a in arrays.values())
+    if per_group * n > DUMP_LIMIT:
+        keep = (DUMP_LIMIT - 64 * 1024) // (per_group + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        arrays = dict({k: a[..., idx] for k, a in arrays.items()}, group_index=idx)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype.kind in "ui" and a.size and int(a.max()) >= 1 << 53:
+            raise SystemExit(f"bench.py --dump-outputs: {name} holds values float64 cannot carry exactly")
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def guarded(fn, *a, **kw):
     """A side measurement must never cost the headline its JSON line: whatever goes wrong in it (a device out of memory on
     a shared box, a fault the stream check raises) is reported in its place."""
@@ -841,7 +863,13 @@ def main():
                     help="kernel variant of the config-5 lines under other_configs (5 = compact, 0 = lane)")
     ap.add_argument("--cpu-sample-groups", type=int, default=1_000_000)
     ap.add_argument("--cpu-sample-ticks", type=int, default=16)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write what its last step computed (rank 0: the commit index and result word "
+                         "of every group of its shard; N>1: also its replica of every rank's published commit indices) as "
+                         "DIR/<name>.npy in float64, at most 64 MB in all (a fixed, seeded sample of groups beyond that)")
     args = ap.parse_args()
+    if args.dump_outputs and args.side:
+        raise SystemExit("bench.py: --dump-outputs dumps the headline's timed region; --side runs none")
     if args.workload == 5 and not (args.one_engine or args.size_class_engines):
         args.sorted = True  # config 5's layout of record: placed by size class, ONE launch per tick
     if args.sorted:
@@ -1180,10 +1208,13 @@ def main():
                            "full_windows": int(sum((pt.eng.read_column(rg.COL.PFLAGS) & rg.PF.INS_FULL).astype(bool).sum()
                                                    for pt in parts))}
     # replay determinism: the timed replay must land on the state the recorded pass produced
+    last_commit, last_out = [], []
     for j, pt in enumerate(parts):
         commit, out = pt.eng.results()
         if not (np.array_equal(commit, pt.ref_commit) and np.array_equal(out, pt.ref_out)):
             raise SystemExit("timed replay diverged from the recorded pass")
+        last_commit.append(commit)
+        last_out.append(out)
         if distributed and os.environ.get("BENCH_SKIP_VERIFY") != "1":  # (skipped only by RG_PUB_DEBUG measurement builds)
             # every rank's replica must hold every rank's shard: compare against the columns themselves
             rep = pt.eng.published_commit()  # [world][n] out of THIS rank's replica
@@ -1192,6 +1223,11 @@ def main():
             for r in range(world):
                 if not np.array_equal(rep[r], cols_all[r].numpy().view(np.uint64)):
                     raise SystemExit(f"rank {rank}: published commit indices of rank {r} differ from its commit column")
+    if args.dump_outputs and rank == 0:
+        outputs = {"commit": np.concatenate(last_commit), "result": np.concatenate(last_out)}
+        if distributed:
+            outputs["published_commit"] = np.concatenate([pt.eng.published_commit() for pt in parts], axis=1)
+        dump_outputs(args.dump_outputs, outputs)
     pub_stats = parts[0].eng.publish_stats() if distributed else None
     comm_census = None
     if distributed:

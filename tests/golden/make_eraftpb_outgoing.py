@@ -119,7 +119,7 @@ def build(cls, enums):
 
 
 def main():
-    package, enums, messages = M.parse_proto(open(M.PROTO, encoding="utf-8").read())
+    package, enums, messages = M.generator_schema()
     cls = M.build_classes(package, enums, messages)
     types, vectors, limits, doc_case = build(cls, enums)
     head = {"source": "proto/proto/eraftpb.proto (Entry :23-31, Snapshot :33-44, Message :71-92), serialised by the protobuf runtime "

@@ -3,14 +3,15 @@
 
 Run in the build container (where /root/reference exists):
 
-    python tests/golden/make_eraftpb_vectors.py          # writes tests/golden/eraftpb_messages.json
+    python tests/golden/make_eraftpb_vectors.py          # writes tests/golden/eraftpb_messages.json + eraftpb_schema.json
 
 The message types are NOT typed in here: the script parses /root/reference/proto/proto/eraftpb.proto (proto3; enums,
 messages, scalar / message / repeated fields -- the whole grammar that file uses), builds the descriptors with the
 protobuf runtime (no protoc in the image) and lets THAT runtime serialise seeded random messages. Every vector is
 `{"hex": <serialised bytes>, "fields": {...}}`; consumers (tests/test_wire_format.py) check rg_decode_message -- the
 decoder behind rg_step_bytes -- against them. A few hand-made malformed byte strings (truncated varint, a length that
-runs past the end, a group wire type) carry `"error": true`.
+runs past the end, a group wire type) carry `"error": true`. What the parser read out of the .proto is kept as data in
+eraftpb_schema.json, so that `--check` and the differential tests run where the reference is absent.
 """
 import json
 import os
@@ -20,6 +21,7 @@ import sys
 
 PROTO = "/root/reference/proto/proto/eraftpb.proto"
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "eraftpb_messages.json")
+SCHEMA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "eraftpb_schema.json")
 
 SCALARS = {"uint64": 4, "uint32": 13, "int64": 3, "int32": 5, "bool": 8, "bytes": 12, "string": 9}  # FieldDescriptorProto.Type
 
@@ -36,6 +38,39 @@ def parse_proto(text):
             messages[name] = [(lab or "", typ, fname, int(num))
                               for lab, typ, fname, num in re.findall(r"(repeated\s+)?([\w.]+)\s+(\w+)\s*=\s*(\d+)\s*;", body)]
     return package, enums, messages
+
+
+def schema_text(package, enums, messages):
+    """eraftpb_schema.json: what parse_proto read out of eraftpb.proto, as data (names, numbers, labels, types)."""
+    def table(d):  # one enum / message per line
+        return "{\n" + ",\n".join(f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in d.items()) + "\n }"
+    return ('{\n "source": "proto/proto/eraftpb.proto, parsed by tests/golden/make_eraftpb_vectors.py",\n'
+            f' "package": {json.dumps(package)},\n "enums": {table(enums)},\n "messages": {table(messages)}\n}}\n')
+
+
+def load_schema():
+    """(package, enums, messages) as parse_proto returns them, from the committed eraftpb_schema.json."""
+    doc = json.load(open(SCHEMA, encoding="utf-8"))
+    return (doc["package"], {k: [tuple(x) for x in v] for k, v in doc["enums"].items()},
+            {k: [tuple(x) for x in v] for k, v in doc["messages"].items()})
+
+
+def generator_schema():
+    """The schema a generator builds its vectors from: parsed out of eraftpb.proto where that file exists (writing
+    eraftpb_schema.json, or with --check comparing against it), else the committed eraftpb_schema.json (--check only)."""
+    check = "--check" in sys.argv
+    if not os.path.exists(PROTO):
+        if not check:
+            raise SystemExit(f"{PROTO} not found: the vectors are generated from the reference's eraftpb.proto")
+        return load_schema()
+    schema = parse_proto(open(PROTO, encoding="utf-8").read())
+    text = schema_text(*schema)
+    if check:
+        if not os.path.exists(SCHEMA) or open(SCHEMA, encoding="utf-8").read() != text:
+            sys.exit(1)
+    else:
+        open(SCHEMA, "w").write(text)
+    return schema
 
 
 def build_classes(package, enums, messages):
@@ -141,7 +176,7 @@ def rand_u64(rng):
 
 
 def main():
-    package, enums, messages = parse_proto(open(PROTO, encoding="utf-8").read())
+    package, enums, messages = generator_schema()
     cls = build_classes(package, enums, messages)
     Message, Entry, Snapshot = cls["Message"], cls["Entry"], cls["Snapshot"]
     types = dict(enums["MessageType"])

@@ -103,3 +103,27 @@ def test_the_line_of_a_multi_gpu_run_fits_and_parses():
     d = _check(bench.line_text(full), bench)
     assert d["cpu_baseline"] is None and d["config"]["rccl_ranks"] == 8 and d["config"]["pub_bytes_per_rank_delta"] == 1000448
     assert d["config"]["pub_compare_value"] == 1.9e10 and d["config"]["publish_auto_exchange_us"] == 44.0
+
+
+def test_dump_outputs_writes_float64_within_the_limit_and_samples_the_same_groups(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float64, values exact; beyond DUMP_LIMIT the same seeded sample of groups
+    from every array, named in group_index.npy."""
+    import numpy as np
+    bench = _bench()
+    commit = np.arange(1000, dtype=np.uint64) * 3 + (1 << 40)
+    result = (np.arange(1000, dtype=np.uint32) * 7) | (1 << 31)
+    bench.dump_outputs(str(tmp_path / "whole"), {"commit": commit, "result": result})
+    got = {n: np.load(tmp_path / "whole" / f"{n}.npy") for n in ("commit", "result")}
+    assert all(a.dtype == np.float64 for a in got.values()) and not (tmp_path / "whole" / "group_index.npy").exists()
+    assert np.array_equal(got["commit"].astype(np.uint64), commit) and np.array_equal(got["result"].astype(np.uint32), result)
+
+    n = 5_000_000  # 2 arrays x 8 B x 5 M groups = 80 MB: sampled
+    big = {"commit": np.arange(n, dtype=np.uint64), "result": np.arange(n, dtype=np.uint32) % 5}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["commit.npy", "group_index.npy", "result.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT
+    idx = np.load(tmp_path / "a" / "group_index.npy").astype(np.int64)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "group_index.npy")) and (np.diff(idx) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "commit.npy"), idx) and np.array_equal(np.load(tmp_path / "a" / "result.npy"), idx % 5)

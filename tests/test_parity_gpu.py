@@ -643,6 +643,45 @@ def test_bench_two_ranks_sharing_the_gpu(rg, tmp_path):
     assert len(line) <= 6000
 
 
+
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat_exactly(rg, tmp_path):
+    """`bench.py --dump-outputs DIR`, twice with the same arguments: identical files, and they hold what one engine stepped
+    through the same seeded stream here (commit index and result word of every group after the W + K ticks)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    G, P, W, K, SEED = 40_000 + 7, 5, 2, 4, 0x5EED5EED
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--groups", str(G), "--slots", str(P),
+               "--steps", str(K), "--warmup", str(W), "--repeats", "2", "--no-cpu-baseline", "--no-extras",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(r.stdout.strip().splitlines()[-1])
+        assert d["steps"] == K and d["warmup"] == W and d["ms_per_step"] > 0
+        assert sorted(os.listdir(out)) == ["commit.npy", "result.npy"]
+        dumps.append({n: np.load(out / f"{n}.npy") for n in ("commit", "result")})
+    for n in ("commit", "result"):
+        assert dumps[0][n].dtype == np.float64 and dumps[0][n].shape == (G,)
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+    eng = rg.Engine(G, P)
+    eng.workload_init(2, seed=SEED)
+    cols = [torch.zeros((P, eng.stride), dtype=torch.int64, device="cuda") for _ in range(4)]
+    flags = torch.zeros((G, 8), dtype=torch.uint8, device="cuda")
+    for t in range(W + K):
+        eng.workload_gen(2, t, *[c.data_ptr() for c in cols], flags.data_ptr(), seed=SEED)
+        eng.tick_device(*[c.data_ptr() for c in cols], flags.data_ptr())
+    commit, res = eng.results()
+    eng.close()
+    assert np.array_equal(dumps[0]["commit"], commit.astype(np.float64))
+    assert np.array_equal(dumps[0]["result"], res.astype(np.float64))
+    assert (commit > 0).all()
+
 def test_device_info_is_queried_not_assumed(rg):
     eng = rg.Engine(1000, 5)
     info = eng.device_info()

@@ -304,7 +304,7 @@ dist.init_process_group("gloo")
 rank, world = dist.get_rank(), dist.get_world_size()
 torch.cuda.set_device(0)  # every rank shares the box's one GPU
 # BASELINE configs[3]'s shape: 7-peer groups sharded over 8 ranks, >= 128 k groups per rank, a publication after EVERY tick
-G, P, WL, RING, TICKS, LOSER = 131_072 + 5, 7, rg.WL_MAJORITY, 4, 19, 5
+G, P, WL, RING, TICKS, LOSER = 131_072 + 5, 7, rg.WL_MAJORITY, 4, 19, min(5, world - 1)
 
 class Dev:
     def __init__(self, ptr, n):
@@ -392,6 +392,19 @@ def test_eight_ranks_of_the_config4_shape_publish_every_tick_with_one_rollback(r
     assert "PUBLISH8_OK 8" in r.stdout, r.stdout[-3000:]
 
 
+
+def test_three_ranks_sharing_the_gpu_publish_every_tick_with_one_rollback(rg, tmp_path):
+    """The eight-rank worker above with three ranks on the GPU (rank 2 rolls back): the same loss -> full-snapshot
+    protocol and tick-by-tick replica checks at another rank count."""
+    script = tmp_path / "worker8.py"
+    script.write_text(WORKER8)
+    env = dict(os.environ, RG_ROOT=ROOT)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3",
+           "--master-addr", "127.0.0.1", "--master-port", "29577", str(script)]
+    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-4000:]
+    assert "PUBLISH8_OK 3" in r.stdout, r.stdout[-3000:]
+
 def test_bench_line_of_eight_ranks_sharing_the_gpu(rg):
     """`bench.py --gpus 8 --slots 7` as the driver launches it (torch.distributed.run, one rank per GPU) -- here with
     BENCH_SHARE_GPU=1 (all ranks on GPU 0, gloo moving the slices): the N = 8 line's JSON end to end."""
@@ -421,6 +434,24 @@ def test_bench_line_of_eight_ranks_sharing_the_gpu(rg):
     assert full["config"]["publication_compare"]["bytes_per_rank_per_publication"] == pub["bytes_per_rank_full"]
     assert line["roofline"]["regime"] in ("infinity-cache", "hbm") and line["cpu_baseline"] is None
 
+
+
+def test_bench_line_of_three_ranks_sharing_the_gpu(rg):
+    """`bench.py --gpus 3 --slots 7` with the three ranks on GPU 0 (BENCH_SHARE_GPU=1): the N = 3 line end to end."""
+    env = dict(os.environ, BENCH_SHARE_GPU="1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=3", "--master-addr", "127.0.0.1",
+           "--master-port", "29576", os.path.join(ROOT, "bench.py"), "--gpus", "3", "--slots", "7", "--groups", "131072",
+           "--steps", "6", "--warmup", "2", "--publish-every", "1"]
+    r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    assert len([ln for ln in r.stdout.splitlines() if ln.strip()]) == 1, r.stdout[-3000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["n_gpus"] == 3 and line["steps"] == 6 and line["scaling"] == "weak"
+    assert line["value"] == pytest.approx(3 * 131072 * 6 / (line["ms_per_step"] * 6 / 1e3), rel=1e-6)
+    cfg = line["config"]
+    assert "configs[3]" in cfg["workload"] and "sharded over 3 GPUs" in cfg["workload"] and cfg["peer_slots"] == 7
+    assert cfg["pub_publications"] >= 6 + 2 and cfg["pub_bytes_per_rank_delta"] < 1.1 * 131072 + 4096 <= cfg["pub_bytes_per_rank_full"]
+    assert cfg["transport"] == "callback" and cfg["rccl_ranks"] == 0 and cfg["rccl_engines"] == 0 and cfg["rccl_distinct_ranks"] == 0
 
 def test_bench_starts_its_own_ranks_with_strong_scaling_and_an_automatic_cadence(rg):
     """The PLAIN command line -- `python bench.py --gpus 2 ...`, no launcher, what the driver runs at N = 1 -- starts its own

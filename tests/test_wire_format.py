@@ -70,7 +70,6 @@ def test_the_test_encoder_reproduces_the_runtime():
     assert n > 100
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/proto/proto/eraftpb.proto"), reason="reference tree not present")
 def test_committed_vectors_are_what_the_generator_produces():
     r = subprocess.run([sys.executable, os.path.join(HERE, "golden", "make_eraftpb_vectors.py"), "--check"])
     assert r.returncode == 0, "tests/golden/eraftpb_messages.json is out of date: rerun make_eraftpb_vectors.py"
@@ -113,9 +112,9 @@ def test_decoder_survives_mutated_and_random_bytes(rg):
     assert n_ok > 3000 and n_bad > 3000, (n_ok, n_bad)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/proto/proto/eraftpb.proto"), reason="reference tree not present")
 def test_decoder_agrees_with_the_protobuf_runtime_on_mutated_bytes(rg):
-    """Differential: the protobuf runtime, with descriptors parsed out of the reference's eraftpb.proto, accepts exactly
+    """Differential: the protobuf runtime, with descriptors built from tests/golden/eraftpb_schema.json (the reference's
+    eraftpb.proto as data; make_eraftpb_vectors.py --check compares the two where the .proto is present), accepts exactly
     the byte strings rg_decode_message accepts, and reads the same fields (nested entries / snapshots are validated, unknown
     fields and well-formed groups skipped, tags beyond 32 bits refused) -- with the one rule where the Python runtime and the
     reference's Rust codecs part: a field of the schema that arrives with another wire type than the declared one is an
@@ -124,7 +123,7 @@ def test_decoder_agrees_with_the_protobuf_runtime_on_mutated_bytes(rg):
     sys.path.insert(0, os.path.join(HERE, "golden"))
     import make_eraftpb_vectors as M
     from raft_rs_amd.engine import decode_message, EngineError
-    package, enums, messages = M.parse_proto(open(M.PROTO, encoding="utf-8").read())
+    package, enums, messages = M.load_schema()
     Message = M.build_classes(package, enums, messages)["Message"]
     rng = np.random.default_rng(4242)
     n_ok = n_strict = 0
@@ -248,23 +247,21 @@ def test_encoder_refuses_what_it_cannot_write(rg):
     assert encode_message({}) == b""  # Message::default(): zero bytes
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/proto/proto/eraftpb.proto"), reason="reference tree not present")
 def test_committed_outgoing_vectors_are_what_the_generator_produces():
     r = subprocess.run([sys.executable, os.path.join(HERE, "golden", "make_eraftpb_outgoing.py"), "--check"])
     assert r.returncode == 0, "tests/golden/eraftpb_outgoing.json is out of date: rerun make_eraftpb_outgoing.py"
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/proto/proto/eraftpb.proto"), reason="reference tree not present")
 def test_encoder_agrees_with_the_protobuf_runtime_on_random_messages(rg):
-    """Differential, 5 000 seeded messages the committed vectors do not hold: the runtime (descriptors parsed out of the
-    reference's eraftpb.proto) parses what rg_encode_message wrote into a message EQUAL to the one it built from the same
+    """Differential, 5 000 seeded messages the committed vectors do not hold: the runtime (descriptors built from
+    tests/golden/eraftpb_schema.json, the reference's eraftpb.proto as data) parses what rg_encode_message wrote into a message EQUAL to the one it built from the same
     content, serialises that to the same bytes, and its ByteSize() is rg_message_size."""
     import random
     sys.path.insert(0, os.path.join(HERE, "golden"))
     import make_eraftpb_vectors as M
     import make_eraftpb_outgoing as MO
     from raft_rs_amd.engine import encode_message
-    package, enums, messages = M.parse_proto(open(M.PROTO, encoding="utf-8").read())
+    package, enums, messages = M.load_schema()
     cls = M.build_classes(package, enums, messages)
     Message, Entry, Snapshot = cls["Message"], cls["Entry"], cls["Snapshot"]
     rng = random.Random(777)
