@@ -391,6 +391,10 @@ extern "C" int rg_tick_device_fused(rg_engine *h, const rg_msgs *m, uint32_t n_t
         u32 e = t;
         while (e < n_ticks && !m[e].m_logterm) e++;
         if (e > t) {
+            // (commit publication: a log-term tick before this launch may have put the slice-complete event on its own
+            // dispatch packet; k_tick_fused writes the same slice behind it, so rg_publish_commit must record its own event.
+            // The copies and k_count_out behind a log-term tick do not touch the slice: a last log-term tick keeps the ride.)
+            h->pub_tick_evt = -1;
             int rc = rg_fused_run(h, m, t, e - t, dev_out_t, dev_commit_t);
             if (rc) return rc;
         }

@@ -8,6 +8,18 @@
 // state[]: match next pr_commit pend_snap pend_rs gid pflags commit term_lo term_hi cfg out
 //          run_first run_term dummy_index dummy_term cur_term host_hint run_count   (19 pointers)
 // msg[]:   m_index m_commit m_hint m_rs m_flags m_logterm       (6 pointers)
+// Commit publication (rg_publish.h): a host slice laid out as rg_pub_layout(G, cap) that the single-threaded entry points below
+// accumulate into, exactly as the kernels accumulate into the engine's send buffer (rg_pub_load / rg_pub_store through the same
+// store paths). Attached with rg_host_check_pub_attach, detached with a null slice; nothing is attached by default (st.pub = nullptr).
+static char *g_pub = nullptr;
+static u32 g_pub_cap = 0;
+
+extern "C" int rg_host_check_pub_attach(void *slice, unsigned cap) {
+    g_pub = (char *)slice;
+    g_pub_cap = cap;
+    return 0;
+}
+
 static RgState make_state(void *const *p, u64 G, u64 stride) {
     RgState st;
     st.match = (u64 *)p[0]; st.next = (u64 *)p[1]; st.prc = (u64 *)p[2]; st.psnap = (u64 *)p[3];
@@ -19,7 +31,8 @@ static RgState make_state(void *const *p, u64 G, u64 stride) {
     // (p[18] = RG_COL_RUN_COUNT: it must sit `stride` bytes behind p[17], as in the engine's arena -- rg_run_n)
     if ((u8 *)p[18] != (u8 *)p[17] + stride) __builtin_trap();
     st.G = G; st.stride = stride;
-    st.pub = nullptr; st.pub_off_delta = 0; st.pub_cap = 0; st.ix64 = 0;
+    st.pub = g_pub; st.pub_off_delta = g_pub ? rg_pub_layout(G, g_pub_cap).off_delta : 0; st.pub_cap = g_pub ? g_pub_cap : 0;
+    st.ix64 = 0;
     return st;
 }
 // RG_PF_PEND_SNAP / RG_PF_PEND_RS are engine-owned: the library derives it when the columns are loaded (k_fix_pending); the arrays a test hands
@@ -88,7 +101,7 @@ template <int P> static void host_fused(const RgState &st, const RgMsgs *ms, u32
             const u64 o = (u64)p * st.stride + g;
             r.mt[p] = st.match[o]; r.pc[p] = st.prc[o]; r.nx[p] = 0;
         }
-        r.dirty = 0; r.evm = 0; r.adv = 0;
+        r.dirty = 0; r.evm = 0; r.adv = rg_pub_load(st, g); // (k_tick_fused: the launch's total advance lands in the byte)
         for (u32 t = 0; t < T; t++) {
             r.mf = ms[t].mflags[g];
             for (int p = 0; p < P; p++) {
@@ -136,6 +149,7 @@ extern "C" int rg_host_check_tick(unsigned P, unsigned long G, unsigned long str
 extern "C" int rg_host_check_tick_mt(unsigned P, unsigned long G, unsigned long stride, void *const *state,
                                      const void *const *msg, int group_commit_kernel, unsigned n_threads) {
     if (P == 0 || P > 8 || n_threads == 0) return -1;
+    if (g_pub) return -1; // (the host twin of the slice's list counter is not atomic: publication runs single-threaded only)
     const RgState st = make_state(state, G, stride);
     const RgMsgs ms = make_msgs(msg);
     const bool gc = group_commit_kernel != 0;

@@ -294,3 +294,183 @@ def test_random_api_sequences_with_the_send_stage(rg, seed, P, cap, mailbox):
     if mailbox:
         assert eng.mailbox_stats()[0] > 0, "no flush was served by the resident workgroup"
     eng.close()
+
+
+def _to_device(torch, msgs, with_logterm):
+    keys = ("m_index", "m_commit", "m_hint", "m_rs", "m_flags")
+    cols = [torch.from_numpy(np.ascontiguousarray(msgs[k]).view(np.uint8 if k == "m_flags" else np.int64).copy()).cuda()
+            for k in keys]
+    if with_logterm:  # (a log-term column without log-term rejects: the tick takes the single-tick road inside a fused call)
+        cols.append(torch.zeros_like(cols[0]))
+    return cols
+
+
+@pytest.mark.parametrize("seed,P", [(21, 3), (22, 5)])
+def test_random_api_sequences_with_publication(rg, seed, P):
+    """Random sequences of entry points on an engine that publishes its commit indices (RCCL at world size 1): dense ticks from
+    host and device buffers, fused calls with and without log-term ticks, sparse ticks, mirror flushes, rg_recompute,
+    rg_set_config, checkpoint / restore, rg_load_column(COMMIT) and rg_permute_groups, the state checked against the oracle
+    after every call, and a publication after about a third of the calls. After every publication the replica equals the commit
+    column -- except inside a loss window (include/raftgroups.h: rg_restore, a reloaded commit column, rg_permute_groups mark
+    the slice lost): the replica may be inexact for at most 2 x ring_ticks publications after the loss, and the one after those
+    at the latest is the loss's one full publication (the check point after the one that folds the lost slice)."""
+    import torch
+    from raft_rs_amd import engine as E
+    COL = rg.COL
+    rng = np.random.default_rng(4500 + seed)
+    G, RING = 1500, 3
+    st = O.alloc_state(G, P)
+    st["cfg"][:] = fuzz.random_cfg(rng, G, P)
+    fuzz.random_state(rng, st, small_values=True)
+    self_slot = ((st["cfg"] >> 16) & 7).astype(np.int64)
+    eng = rg.Engine(G, P)
+    eng.load_state(st)
+    for g in range(G):
+        eng.set_peers(g, list(range(1, P + 1)), TERM)
+    cl = O.Cluster(G)
+    cl.load_soa(st, term=TERM)
+    eng.comm_init(0, 1, unique_id=E.comm_unique_id(), ring_ticks=RING)
+    msgs = O.alloc_msgs(G, P)
+    del msgs["m_logterm"]
+    mb = rg.MsgBuffers(G, P, eng.stride)
+    gout = np.zeros(G, dtype=np.uint32)
+    out_t = torch.zeros((8, G), dtype=torch.int32, device="cuda")
+    ckpt, window = None, None  # window: [publications since the loss, this one included; full publications before it]
+    ops_seen, windows_closed, exact_checks = set(), 0, 0
+    LOSS = ("restore", "load_commit", "permute")
+
+    def reload_oracle():
+        nonlocal cl
+        cl = O.Cluster(G)
+        cl.load_soa(st, term=TERM)
+
+    def publish():
+        nonlocal window, windows_closed, exact_checks
+        eng.publish_commit()
+        fulls = eng.publish_stats()["full_publications"]
+        exact = np.array_equal(eng.published_commit(0), eng.read_column(COL.COMMIT))
+        if window is None:
+            assert exact and fulls == full_base[0], (step, op, fulls, full_base)
+            exact_checks += 1
+            return
+        window[0] += 1
+        assert fulls <= window[1] + 1, (step, "more than one full publication for one loss", fulls, window)
+        if fulls == window[1] + 1:
+            assert exact and window[0] <= 2 * RING + 1, (step, window, exact)
+            full_base[0] = fulls
+            window, windows_closed = None, windows_closed + 1
+        else:
+            assert window[0] <= 2 * RING, (step, "the loss window did not close", window)
+
+    full_base = [eng.publish_stats()["full_publications"]]
+    assert full_base[0] == 1
+    for step in range(90):
+        cl.store_soa(st)
+        op = rng.choice(["dense", "device", "fused", "fused_lt", "sparse3", "sparse1", "mirror_sparse", "mirror_dense", "recompute",
+                         "set_config", "checkpoint", "restore", "load_commit", "permute"],
+                        p=[0.1, 0.1, 0.08, 0.1, 0.08, 0.08, 0.08, 0.06, 0.06, 0.06, 0.05, 0.05, 0.05, 0.05])
+        if op == "restore" and ckpt is None:
+            op = "checkpoint"
+        if op in LOSS and window is not None:
+            op = "dense"  # (one loss at a time: each window is checked for its own full publication)
+        ops_seen.add(op)
+        if op == "checkpoint":
+            eng.checkpoint()
+            ckpt = ({k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in st.items()}, self_slot.copy())
+        elif op == "restore":
+            eng.restore()
+            st = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in ckpt[0].items()}
+            self_slot = ckpt[1].copy()
+            reload_oracle()
+        elif op == "load_commit":
+            # a host reloads the commit column (here: some groups raised to their last index, the rest as they are)
+            c = st["commit"].copy()
+            up = rng.choice(G, size=40, replace=False)
+            c[up] = np.maximum(c[up], np.minimum(st["term_hi"][up], c[up] + 3))
+            eng.load_column(COL.COMMIT, c)
+            st["commit"][:] = c
+            reload_oracle()
+        elif op == "permute":
+            perm = rng.permutation(G).astype(np.uint64)
+            eng.permute_groups(perm)
+            p = perm.astype(np.int64)
+            for k in ("match", "next", "pr_commit", "pend_snap", "pend_rs", "gid"):
+                st[k][:, :G] = st[k][:, p]
+            for k in ("pflags", "commit", "term_lo", "term_hi", "cfg"):
+                st[k][:] = st[k][p]
+            self_slot = self_slot[p]
+            ckpt = None  # (rg_permute_groups drops the checkpoint: it images the old placement)
+            reload_oracle()
+        elif op == "set_config":
+            for g in rng.choice(G, size=5, replace=False):
+                w = int(fuzz.random_cfg(rng, 1, P)[0])
+                eng.set_config(int(g), w)
+                st["cfg"][g] = w
+                self_slot[g] = (w >> 16) & 7
+            reload_oracle()
+        elif op == "recompute":
+            eng.recompute()
+            for g in range(G):
+                gout[g] = 1 if cl.maybe_commit(g) else 0
+        elif op in ("fused", "fused_lt"):
+            T = int(rng.integers(1, 5))
+            kinds = ["plain"] * T
+            if op == "fused_lt":
+                kinds[int(rng.integers(0, T))] = "lt"
+            dev = []
+            for t in range(T):
+                cl.store_soa(st)
+                fuzz.random_msgs(rng, st, msgs)
+                gout[:] = 0
+                cl.tick_soa(msgs, gout)
+                dev.append(_to_device(torch, msgs, kinds[t] == "lt"))
+            assert eng.tick_device_fused([[c.data_ptr() for c in d] for d in dev], out_t.data_ptr()) == T
+            eng.sync()
+        else:
+            fuzz.random_msgs(rng, st, msgs)
+            touched = None
+            if op in ("sparse3", "sparse1", "mirror_sparse"):
+                touched = np.sort(rng.choice(G, size=int(rng.integers(1, G // 3)), replace=False))
+                keep = np.zeros(G, dtype=bool)
+                keep[touched] = True
+                msgs["m_flags"][~keep] = 0
+            if op.startswith("mirror"):
+                clean_for_mirror(msgs, P, self_slot)
+            if op == "dense":
+                for k in ("m_index", "m_commit", "m_hint", "m_rs", "m_flags"):
+                    getattr(mb, k)[...] = msgs[k]
+                eng.tick(mb)
+            elif op == "device":
+                d = _to_device(torch, msgs, False)
+                eng.tick_device(*[c.data_ptr() for c in d])
+                eng.sync()
+            elif op == "sparse3":
+                assert eng.ingest(records(msgs, touched, P, rng)) == 0
+                eng.tick_ingested()
+            elif op == "sparse1":
+                assert eng.ingest_tick(records(msgs, touched, P, rng))[1] == 0
+            else:
+                mirror_steps(rg, eng, msgs, touched if touched is not None else range(G), P, self_slot)
+                eng.flush()
+            gout[:] = 0
+            cl.tick_soa(msgs, gout)
+        if op in LOSS:
+            window = [0, full_base[0]]
+        if op not in ("checkpoint",):
+            got = eng.read_state()
+            cl.store_soa(st)
+            diffs = fuzz.diff_states(st, got, G, P)
+            assert not diffs, (step, op, diffs[:5])
+            if op not in LOSS + ("set_config",):
+                assert (got["out"] == gout).all(), (step, op, np.nonzero(got["out"] != gout)[0][:5])
+        if rng.random() < 1 / 3:
+            publish()
+    for _ in range(2 * RING + 1):  # (a window still open at the end must close as well)
+        if window is None:
+            break
+        op = "final"
+        publish()
+    assert window is None
+    assert windows_closed >= 2 and exact_checks >= 5, (windows_closed, exact_checks)
+    assert {"fused_lt", "permute", "load_commit", "restore", "mirror_dense", "recompute"} <= ops_seen, ops_seen
+    eng.close()

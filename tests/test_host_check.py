@@ -980,3 +980,128 @@ def test_window_arithmetic_equals_a_plain_queue(cap, spread):
         assert deep > 4 and (modes == 0).any() and (modes[1:][(modes[:-1] == 0)] == 1).any()  # ... deeper ones in the ring, and back
     if spread >= (1 << 22) and cap >= 3:
         assert (modes[counts >= 2] == 0).any()  # a distance beyond 21 bits forces the ring
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Commit publication on the host twin: the slice the store paths accumulate into (rg_pub_load / rg_pub_store /
+# rg_pub_accumulate, rg_publish.h) against rg_pub_accumulate_host applied once per interval (start -> end of the interval),
+# compared in canonical form (tests/pubcheck.py), and the decoded advance against the oracle's commit column.
+# ---------------------------------------------------------------------------------------------------------------
+import pubcheck  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def pub_attach():
+    if build_lib() is None:
+        pytest.skip("hipcc not available")
+    fn = C.CDLL(LIB).rg_host_check_pub_attach
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_uint]
+
+    def attach(sl, cap):
+        assert fn(None if sl is None else sl.ctypes.data, cap) == 0
+    return attach
+
+
+def _pub_intervals(twin, pub_attach, P, gc, base, intervals, G, cap, adv_of):
+    """Drive `twin(eng_st, ticks)` over publication intervals of crafted acks; after each interval compare the twin's slice
+    with the host accumulate and the oracle. Returns the slices' headers."""
+    from raft_rs_amd import engine as E
+    st = pubcheck.crafted_state(G, P, base, gc)
+    cl = O.Cluster(G)
+    cl.load_soa(st, term=6)
+    eng_st = copy_state(st)
+    sl = pubcheck.new_slice(G, cap)
+    gout = np.zeros(G, dtype=np.uint32)
+    headers = []
+    pub_attach(sl, cap)
+    try:
+        for i, T in enumerate(intervals):
+            adv = adv_of(i, T)
+            c0 = eng_st["commit"].copy()
+            cur, ticks = c0.copy(), []
+            for t in range(T):
+                ticks.append(pubcheck.ack_msgs(O.alloc_msgs(G, P), cur, cur + adv[t]))
+                cur = cur + adv[t]
+            for m in ticks:
+                cl.tick_soa(m, gout)
+            cl.store_soa(st)
+            twin(eng_st, ticks)
+            assert not fuzz.diff_states(st, eng_st, G, P), i
+            assert (eng_st["commit"] == cur).all(), (i, "the crafted advances did not commit", np.nonzero(eng_st["commit"] != cur)[0][:5])
+            want = pubcheck.new_slice(G, cap)
+            E.pub_accumulate_host(c0, st["commit"], want, cap)
+            pubcheck.assert_same_slice(sl, want, G, cap, (i, T))
+            if not pubcheck.canonical(sl, G, cap)[4]:
+                assert (pubcheck.decode(sl, G, cap) == st["commit"] - c0).all(), i
+            headers.append(pubcheck.header(sl))
+            sl[:] = 0  # (rg_pub_post: the slice starts its next interval empty)
+    finally:
+        pub_attach(None, 0)
+    return headers
+
+
+@pytest.mark.parametrize("base", [0, 2**62])
+@pytest.mark.parametrize("gc", [False, True])
+@pytest.mark.parametrize("n_slots", [1, 3, 5, 8])
+@pytest.mark.parametrize("mode", ["tick", "fused", "tick_then_fused", "tick_send"])
+def test_publication_slice_of_the_store_paths_equals_the_host_accumulate(host_tick, host_fused, host_tick_send, pub_attach,
+                                                                         mode, n_slots, gc, base):
+    """Intervals of 1..3 ticks, as single ticks (rg_store_group), one fused run (k_tick_fused's sum of r.adv over its ticks),
+    a tick followed by a fused run, or tick + send stage in one pass: advances 0 .. 2^32 + 3 and bytes that cross 255 only on
+    the second or third tick of an interval (inside one fused run as well), G = 2053 (no multiple of 8 or 256) with its last
+    group advancing, near the top of the index range too."""
+    G = 2053
+    cap = pubcheck.default_cap(G)
+    ins_cap = 4
+    meta = np.zeros((n_slots, 2304), dtype=np.uint32)
+    head = (np.zeros((n_slots, 2304), dtype=np.uint64), np.zeros((n_slots, 2304), dtype=np.uint64))
+    ring = np.zeros((G, n_slots, ins_cap), dtype=np.uint64)
+
+    def twin(eng_st, ticks):
+        out = np.zeros(G, dtype=np.uint32)
+        if mode == "tick":
+            for m in ticks:
+                host_tick(eng_st, m, out, gc)
+        elif mode == "tick_send":
+            for m in ticks:
+                host_tick_send(eng_st, m, out, gc, meta, head, ring, ins_cap, 0)
+        else:
+            first = ticks[:1] if mode == "tick_then_fused" and len(ticks) > 1 else []
+            for m in first:
+                host_tick(eng_st, m, out, gc)
+            rest = ticks[len(first):]
+            out_t = np.zeros((len(rest), G), dtype=np.uint32)
+            commit_t = np.zeros((len(rest), G), dtype=np.uint64)
+            host_fused(eng_st, rest, out, out_t, commit_t, gc)
+
+    headers = _pub_intervals(twin, pub_attach, n_slots, gc, base, [1, 2, 3, 3, 1, 2], G, cap,
+                             lambda i, T: pubcheck.pattern_advances(G, T, seed=i))
+    assert all(n > 0 for n, _ in headers), headers  # every interval went through the exact list
+
+
+@pytest.mark.parametrize("mode", ["tick", "fused"])
+@pytest.mark.parametrize("extra", [0, 1])
+def test_publication_list_filled_to_its_capacity_and_one_beyond(host_tick, host_fused, pub_attach, mode, extra):
+    """`cap` saturated groups fill the list exactly (no loss); `cap + 1` sets RG_PUB_LOST (and only then)."""
+    G, P, cap = 1029, 3, 16
+    n_sat = cap + extra
+
+    def twin(eng_st, ticks):
+        out = np.zeros(G, dtype=np.uint32)
+        if mode == "tick":
+            for m in ticks:
+                host_tick(eng_st, m, out, False)
+        else:
+            host_fused(eng_st, ticks, out, np.zeros((len(ticks), G), dtype=np.uint32),
+                       np.zeros((len(ticks), G), dtype=np.uint64), False)
+
+    def adv_of(i, T):
+        a = np.full((T, G), 3, dtype=np.uint64)
+        sat = np.linspace(0, G - 1, n_sat).astype(np.int64)  # (group G - 1 among them)
+        a[0, sat] = 256 + np.arange(n_sat, dtype=np.uint64) * 1000
+        return a
+
+    headers = _pub_intervals(twin, pub_attach, P, False, 1000, [1, 1], G, cap, adv_of)
+    for n, flags in headers:
+        assert n == n_sat and bool(flags & pubcheck.PUB_LOST) == (n_sat > cap), (n, flags, n_sat, cap)

@@ -625,3 +625,122 @@ def test_three_engines_one_thread_each(rg):
     for rank in range(world):
         for t in range(ticks):
             assert np.array_equal(out[rank][t], want[t]), (rank, t)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# rg_tick_device_fused with log-term ticks followed by a publication. A log-term tick runs as a single dense tick
+# (rg_tick_impl), which puts the slice-complete event on its own dispatch packet; a fused launch behind it in the same call
+# writes the same slice, so that event must not stand for the slice: rg_publish_commit records its own (events_on_tick_packets
+# unchanged). Only a log-term tick that is the call's last launch keeps the ride.
+# ---------------------------------------------------------------------------------------------------------------
+def _fused_then_publish(rg, G, P, orders, wl=2):
+    import torch
+    from raft_rs_amd import engine as E
+    eng, twin = rg.Engine(G, P), rg.Engine(G, P)
+    for e in (eng, twin):
+        e.workload_init(wl)
+    eng.comm_init(0, 1, unique_id=E.comm_unique_id(), ring_ticks=4)
+    zero_lt = torch.zeros((P, eng.stride), dtype=torch.int64, device="cuda")  # (a log-term column: the pointer is what counts)
+    out_t = torch.zeros((8, G), dtype=torch.int32, device="cuda")
+    k = 0
+    for order in orders:
+        ticks = []
+        for kind in order:  # the twin generates every tick from its state and applies it alone (T x rg_tick_device)
+            cols, flags = _device_msgs(torch, twin, P)
+            twin.workload_gen(wl, k, *[c.data_ptr() for c in cols], flags.data_ptr())
+            lt = zero_lt if kind == "lt" else None
+            twin.tick_device(*[c.data_ptr() for c in cols], flags.data_ptr(), m_logterm=None if lt is None else lt.data_ptr())
+            ticks.append(cols + [flags] + ([lt] if lt is not None else []))
+            k += 1
+        before = eng.publish_stats()["events_on_tick_packets"]
+        assert eng.tick_device_fused([[c.data_ptr() for c in t] for t in ticks], out_t.data_ptr()) == len(order)
+        eng.publish_commit()
+        rode = eng.publish_stats()["events_on_tick_packets"] - before
+        commit = eng.read_column(rg.COL.COMMIT)
+        assert np.array_equal(commit, twin.read_column(rg.COL.COMMIT)), order
+        rep = eng.published_commit(0)
+        bad = np.nonzero(rep != commit)[0]
+        assert bad.size == 0, (order, "replica", bad.size, bad[:5], rep[bad[:5]], commit[bad[:5]])
+        # the slice-complete event may ride on the log-term tick's packet only when nothing was enqueued behind that tick
+        assert rode == (1 if order[-1] == "lt" else 0), (order, rode)
+        del ticks
+    eng.close()
+    twin.close()
+
+
+@pytest.mark.parametrize("order", [("lt", "plain", "plain"), ("plain", "lt", "plain"), ("plain", "plain", "lt"), ("lt",),
+                                   ("plain", "lt", "plain", "plain", "lt", "plain")])
+def test_fused_call_with_log_term_ticks_then_publish(rg, order):
+    """Four fused calls of the same shape, each followed by rg_publish_commit: the replica equals the commit column and the
+    same ticks applied one at a time; events_on_tick_packets moves only when the log-term tick was the call's last launch."""
+    _fused_then_publish(rg, 40_000 + 7, 5, [order] * 4)
+
+
+def test_fused_call_with_a_leading_log_term_tick_then_publish_at_one_million_groups(rg):
+    """1 M x 5: the fused launch behind the log-term tick runs long enough that an exchange ordered only behind the log-term
+    tick would read and reset the slice while that launch is still writing it."""
+    import gc
+    gc.collect()
+    _fused_then_publish(rg, 1 << 20, 5, [("lt", "plain", "plain")] * 3 + [("plain", "lt")])
+
+
+def test_fused_call_stopped_by_a_host_hint_then_publish(rg):
+    """A fused call of log-term ticks that ends early behind a tick leaving a reject to the host (RG_ERR_HOST_HINT), then a
+    publication: the replica equals the commit column the applied ticks produced (the oracle's)."""
+    import torch
+    import fuzz
+    import hosthints
+    from raft_rs_amd import engine as E
+    from raft_rs_amd.engine import COL
+    n_slots = 3
+    rng = np.random.default_rng(9900 + n_slots)  # (tests/test_parity_gpu.py::test_fused_call_stops_behind_a_tick_that_leaves_...)
+    G, TERM, T = 3000, 30, 8
+    st = O.add_term_table(O.alloc_state(G, n_slots))
+    st["cfg"][:] = fuzz.random_cfg(rng, G, n_slots, missing_progress_frac=0.03)
+    fuzz.random_state(rng, st, probe_frac=0.5, base=200)
+    fuzz.random_term_table(rng, st, TERM, min_runs=O.TERM_RUNS)
+    eng = rg.Engine(G, n_slots)
+    eng.load_state(st)
+    eng.comm_init(0, 1, unique_id=E.comm_unique_id(), ring_ticks=4)
+    ahead, host = O.Cluster(G), O.Cluster(G)
+    ahead.load_soa(st, term=TERM)
+    host.load_soa(st, term=TERM)
+    gout = np.zeros(G, dtype=np.uint32)
+    ticks, dev, want_commit = [], [], []
+    for t in range(T):
+        ahead.store_soa(st)
+        msgs = O.alloc_msgs(G, n_slots)
+        fuzz.random_msgs(rng, st, msgs, valid_p=0.8, reject_p=0.6, rs_p=0.05, sent_p=0.2, heartbeat_p=0.05, logterm_max=TERM + t,
+                         elect_p=0.5, elect_term=TERM + 1 + t)
+        hosthints.spread_reject_hints(rng, st, msgs, TERM + 1 + t)
+        ahead.tick_soa(msgs, gout)
+        ahead.store_soa(st)
+        ticks.append(msgs)
+        want_commit.append(st["commit"].copy())
+        dev.append([torch.from_numpy(np.ascontiguousarray(msgs[k]).view(np.uint8 if k == "m_flags" else np.int64).copy()).cuda()
+                    for k in ("m_index", "m_commit", "m_hint", "m_rs", "m_flags", "m_logterm")])
+    out_t = torch.zeros((T, G), dtype=torch.int32, device="cuda")
+    pos, early_stops = 0, 0
+    hgout = np.zeros(G, dtype=np.uint32)
+    while pos < T:
+        n = eng.tick_device_fused([[c.data_ptr() for c in tick] for tick in dev[pos:]], out_t[pos:].data_ptr())
+        eng.publish_commit()
+        commit = eng.read_column(COL.COMMIT)
+        assert np.array_equal(commit, want_commit[pos + n - 1]), (pos, n)
+        assert np.array_equal(eng.published_commit(0), commit), (pos, n)
+        for k in range(n):
+            host.tick_soa(ticks[pos + k], hgout)
+        last = pos + n - 1
+        if pos + n < T:
+            early_stops += 1
+
+            def resolve(recs):
+                assert eng.resolve_host_hints(recs).all()
+                return eng.read_column(COL.OUT)
+
+            hosthints.settle(host, ticks[last], eng.read_column(COL.OUT), eng.read_column(COL.HOST_HINT), resolve=resolve)
+        pos += n
+    assert early_stops >= 2, early_stops
+    eng.publish_commit()
+    assert np.array_equal(eng.published_commit(0), eng.read_column(COL.COMMIT))
+    eng.close()
