@@ -2,8 +2,8 @@
 
     python -m raft_rs_amd.build [--force] [--opt N ...]
 
-hipcc cross-compiles without a GPU. The tick kernels are instantiated once per slot count
-(csrc/tick_inst.hip, -DRG_P=1..8) and compiled in parallel with the ABI units (csrc/abi_*.hip: state / tick /
+hipcc cross-compiles without a GPU. The tick kernels are compiled once per slot count (csrc/tick_inst.hip,
+-DRG_P=1..8: each object holds the kernels of its slot count and the table of their launchers) in parallel with the ABI units (csrc/abi_*.hip: state / tick /
 send / mirror / wire / publish / placement, along the sections of include/raftgroups.h), then linked. Everything is built with
 -fvisibility=hidden: the exported symbols are exactly the entry points the public header declares.
 The .so is git-ignored but travels with gpurun snapshots.

@@ -52,11 +52,7 @@ extern "C" int rg_ingest(rg_engine *h, const rg_wire_msg *records, uint64_t n, u
     if (!h || (!records && n)) return rg_fail(RG_ERR_INVALID_ARG, "rg_ingest: bad argument");
     if (n_duplicates) *n_duplicates = 0;
     if (n == 0) return RG_OK;
-    RG_ENTER(h);
-    {   // (device Inflights: nothing of the next step is enqueued while a host hint of the last one is unanswered)
-        const int hrc__ = rg_require_hints_resolved(h, "rg_ingest");
-        if (hrc__) return hrc__;
-    }
+    RG_ENTER_STEP(h, "rg_ingest");
     int rc = rg_ensure_sparse(h);
     if (rc) return rc;
     if (n > h->d_records_cap) {
@@ -86,11 +82,7 @@ extern "C" int rg_ingest(rg_engine *h, const rg_wire_msg *records, uint64_t n, u
 extern "C" int rg_ingest_device(rg_engine *h, const rg_wire_msg *dev_records, uint64_t n) try {
     if (!h || (!dev_records && n)) return rg_fail(RG_ERR_INVALID_ARG, "rg_ingest_device: bad argument");
     if (n == 0) return RG_OK;
-    RG_ENTER(h);
-    {   // (device Inflights: nothing of the next step is enqueued while a host hint of the last one is unanswered)
-        const int hrc__ = rg_require_hints_resolved(h, "rg_ingest_device");
-        if (hrc__) return hrc__;
-    }
+    RG_ENTER_STEP(h, "rg_ingest_device");
     int rc = rg_ensure_sparse(h);
     if (rc) return rc;
     hipLaunchKernelGGL(k_ingest, dim3(rg_grid(n, RG_INGEST_BLOCK)), dim3(RG_INGEST_BLOCK), 0, h->stream,
@@ -146,16 +138,7 @@ int rg_sparse_enqueue(rg_engine *h, u64 upper, char *packed, bool any_logterm, b
     lo.packed = packed;
     if (one_launch && small_send) { // ... and the touched groups' send stage as well (rg_flush_send)
         if (any_logterm) ms.mhr = h->rhint;
-        switch (h->P) {
-        case 1: rg_launch_flush_small_send_t<1>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo, *small_send); break;
-        case 2: rg_launch_flush_small_send_t<2>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo, *small_send); break;
-        case 3: rg_launch_flush_small_send_t<3>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo, *small_send); break;
-        case 4: rg_launch_flush_small_send_t<4>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo, *small_send); break;
-        case 5: rg_launch_flush_small_send_t<5>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo, *small_send); break;
-        case 6: rg_launch_flush_small_send_t<6>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo, *small_send); break;
-        case 7: rg_launch_flush_small_send_t<7>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo, *small_send); break;
-        default: rg_launch_flush_small_send_t<8>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo, *small_send); break;
-        }
+        h->launch->flush_small_send(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo, *small_send);
         hipError_t e1 = hipGetLastError();
         if (e1 != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "sparse tick + send stage: launch failed: %s", hipGetErrorString(e1));
         h->tick_launches++;
@@ -163,16 +146,7 @@ int rg_sparse_enqueue(rg_engine *h, u64 upper, char *packed, bool any_logterm, b
     }
     if (one_launch) { // <= 256 records: ingest, hint resolution, tick and results in ONE single-workgroup launch
         if (any_logterm) ms.mhr = h->rhint;
-        switch (h->P) {
-        case 1: rg_launch_flush_small_t<1>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo); break;
-        case 2: rg_launch_flush_small_t<2>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo); break;
-        case 3: rg_launch_flush_small_t<3>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo); break;
-        case 4: rg_launch_flush_small_t<4>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo); break;
-        case 5: rg_launch_flush_small_t<5>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo); break;
-        case 6: rg_launch_flush_small_t<6>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo); break;
-        case 7: rg_launch_flush_small_t<7>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo); break;
-        default: rg_launch_flush_small_t<8>(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo); break;
-        }
+        h->launch->flush_small(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo);
         hipError_t e1 = hipGetLastError();
         if (e1 != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "sparse tick: launch failed: %s", hipGetErrorString(e1));
         h->tick_launches++;
@@ -183,16 +157,7 @@ int rg_sparse_enqueue(rg_engine *h, u64 upper, char *packed, bool any_logterm, b
         hipLaunchKernelGGL(k_resolve_hints_list, dim3(rg_grid(upper, RG_BLOCK)), dim3(RG_BLOCK), 0, h->stream, h->st, ms,
                            h->P, h->rhint, (const u64 *)h->list, (const u32 *)h->counters);
     }
-    switch (h->P) {
-    case 1: rg_launch_tick_list_t<1>(h->stream, h->st, ms, h->any_group_commit, h->list, h->counters, upper, mf, lo); break;
-    case 2: rg_launch_tick_list_t<2>(h->stream, h->st, ms, h->any_group_commit, h->list, h->counters, upper, mf, lo); break;
-    case 3: rg_launch_tick_list_t<3>(h->stream, h->st, ms, h->any_group_commit, h->list, h->counters, upper, mf, lo); break;
-    case 4: rg_launch_tick_list_t<4>(h->stream, h->st, ms, h->any_group_commit, h->list, h->counters, upper, mf, lo); break;
-    case 5: rg_launch_tick_list_t<5>(h->stream, h->st, ms, h->any_group_commit, h->list, h->counters, upper, mf, lo); break;
-    case 6: rg_launch_tick_list_t<6>(h->stream, h->st, ms, h->any_group_commit, h->list, h->counters, upper, mf, lo); break;
-    case 7: rg_launch_tick_list_t<7>(h->stream, h->st, ms, h->any_group_commit, h->list, h->counters, upper, mf, lo); break;
-    default: rg_launch_tick_list_t<8>(h->stream, h->st, ms, h->any_group_commit, h->list, h->counters, upper, mf, lo); break;
-    }
+    h->launch->list(h->stream, h->st, ms, h->any_group_commit, h->list, h->counters, upper, mf, lo);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "sparse tick: launch failed: %s", hipGetErrorString(e));
     h->tick_launches++;
@@ -216,11 +181,7 @@ int rg_sparse_finish(rg_engine *h, u64 n_groups) {
 extern "C" int rg_tick_ingested(rg_engine *h, uint64_t *n_groups) try {
     if (!h) return rg_fail(RG_ERR_INVALID_ARG, "rg_tick_ingested: null engine");
     if (n_groups) *n_groups = 0;
-    RG_ENTER(h);
-    {   // (device Inflights: nothing of the next step is enqueued while a host hint of the last one is unanswered)
-        const int hrc__ = rg_require_hints_resolved(h, "rg_tick_ingested");
-        if (hrc__) return hrc__;
-    }
+    RG_ENTER_STEP(h, "rg_tick_ingested");
     int rc = rg_ensure_sparse(h);
     if (rc) return rc;
     const u64 upper = h->ingested_upper < h->G ? h->ingested_upper : h->G;
@@ -784,16 +745,7 @@ static int rg_mailbox_launch(rg_engine *h) {
         ss0.counter = h->send_counter;
         ss0.pin = h->pin_send;
     }
-    switch (h->P) {
-    case 1: rg_launch_mailbox_t<1>(h->stream, h->st, ms, h->any_group_commit, a0, h->counters_base, h->rhint, mf, lo, h->mbox, h->mbox_idle_ticks, max_ticks, ss0); break;
-    case 2: rg_launch_mailbox_t<2>(h->stream, h->st, ms, h->any_group_commit, a0, h->counters_base, h->rhint, mf, lo, h->mbox, h->mbox_idle_ticks, max_ticks, ss0); break;
-    case 3: rg_launch_mailbox_t<3>(h->stream, h->st, ms, h->any_group_commit, a0, h->counters_base, h->rhint, mf, lo, h->mbox, h->mbox_idle_ticks, max_ticks, ss0); break;
-    case 4: rg_launch_mailbox_t<4>(h->stream, h->st, ms, h->any_group_commit, a0, h->counters_base, h->rhint, mf, lo, h->mbox, h->mbox_idle_ticks, max_ticks, ss0); break;
-    case 5: rg_launch_mailbox_t<5>(h->stream, h->st, ms, h->any_group_commit, a0, h->counters_base, h->rhint, mf, lo, h->mbox, h->mbox_idle_ticks, max_ticks, ss0); break;
-    case 6: rg_launch_mailbox_t<6>(h->stream, h->st, ms, h->any_group_commit, a0, h->counters_base, h->rhint, mf, lo, h->mbox, h->mbox_idle_ticks, max_ticks, ss0); break;
-    case 7: rg_launch_mailbox_t<7>(h->stream, h->st, ms, h->any_group_commit, a0, h->counters_base, h->rhint, mf, lo, h->mbox, h->mbox_idle_ticks, max_ticks, ss0); break;
-    default: rg_launch_mailbox_t<8>(h->stream, h->st, ms, h->any_group_commit, a0, h->counters_base, h->rhint, mf, lo, h->mbox, h->mbox_idle_ticks, max_ticks, ss0); break;
-    }
+    h->launch->mailbox(h->stream, h->st, ms, h->any_group_commit, a0, h->counters_base, h->rhint, mf, lo, h->mbox, h->mbox_idle_ticks, max_ticks, ss0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "mailbox: launch failed: %s", hipGetErrorString(e));
     h->mbox_running = true;

@@ -18,16 +18,9 @@ int rg_send_enqueue(rg_engine *h, uint64_t max_entries_per_msg, uint32_t flags, 
     h->send_last_dense = false;
     if (!list && !n_ptr && n == h->G) { // every group: work items into the peer-major columns, no list
         const dim3 grid(rg_grid(h->G, RG_BLOCK)), block(RG_BLOCK);
-        switch (h->P) {
-        case 1: rg_launch_send_dense<1>(h->stream, grid, block, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, h->send_cols); break;
-        case 2: rg_launch_send_dense<2>(h->stream, grid, block, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, h->send_cols); break;
-        case 3: rg_launch_send_dense<3>(h->stream, grid, block, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, h->send_cols); break;
-        case 4: rg_launch_send_dense<4>(h->stream, grid, block, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, h->send_cols); break;
-        case 5: rg_launch_send_dense<5>(h->stream, grid, block, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, h->send_cols); break;
-        case 6: rg_launch_send_dense<6>(h->stream, grid, block, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, h->send_cols); break;
-        case 7: rg_launch_send_dense<7>(h->stream, grid, block, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, h->send_cols); break;
-        default: rg_launch_send_dense<8>(h->stream, grid, block, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, h->send_cols); break;
-        }
+        rg_with_p(h->P, [&](auto p) {
+            rg_launch_send_dense<decltype(p)::value>(h->stream, grid, block, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, h->send_cols);
+        });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "send stage: launch failed: %s", hipGetErrorString(e));
         h->send_cols_fresh = true;
@@ -38,16 +31,10 @@ int rg_send_enqueue(rg_engine *h, uint64_t max_entries_per_msg, uint32_t flags, 
     if (!append) RG_HIP(hipMemsetAsync(h->send_counter, 0, 4, h->stream));
     if (n) {
         const dim3 grid(rg_grid(n, RG_SEND_BLOCK)), block(RG_SEND_BLOCK);
-        switch (h->P) {
-        case 1: hipLaunchKernelGGL(k_send_appends<1>, grid, block, 0, h->stream, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, list, n, n_ptr, h->send_items, h->send_counter); break;
-        case 2: hipLaunchKernelGGL(k_send_appends<2>, grid, block, 0, h->stream, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, list, n, n_ptr, h->send_items, h->send_counter); break;
-        case 3: hipLaunchKernelGGL(k_send_appends<3>, grid, block, 0, h->stream, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, list, n, n_ptr, h->send_items, h->send_counter); break;
-        case 4: hipLaunchKernelGGL(k_send_appends<4>, grid, block, 0, h->stream, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, list, n, n_ptr, h->send_items, h->send_counter); break;
-        case 5: hipLaunchKernelGGL(k_send_appends<5>, grid, block, 0, h->stream, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, list, n, n_ptr, h->send_items, h->send_counter); break;
-        case 6: hipLaunchKernelGGL(k_send_appends<6>, grid, block, 0, h->stream, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, list, n, n_ptr, h->send_items, h->send_counter); break;
-        case 7: hipLaunchKernelGGL(k_send_appends<7>, grid, block, 0, h->stream, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, list, n, n_ptr, h->send_items, h->send_counter); break;
-        default: hipLaunchKernelGGL(k_send_appends<8>, grid, block, 0, h->stream, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, list, n, n_ptr, h->send_items, h->send_counter); break;
-        }
+        rg_with_p(h->P, [&](auto p) {
+            hipLaunchKernelGGL(k_send_appends<decltype(p)::value>, grid, block, 0, h->stream, h->st, h->ins, (u64)max_entries_per_msg, (u32)flags, list, n, n_ptr,
+                               h->send_items, h->send_counter);
+        });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "send stage: launch failed: %s", hipGetErrorString(e));
     }

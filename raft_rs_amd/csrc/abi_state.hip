@@ -39,6 +39,10 @@ extern "C" uint64_t rg_column_bytes(const rg_engine *h, int c) {
     return (uint64_t)h->G * rg_col_elem(c);
 }
 
+// the launcher table of the tick kernels instantiated for P slots (one per tick_inst.hip object)
+const RgTickLaunch &rg_tick_launch(u32 P) {
+    return *rg_with_p(P, [](auto p) { return &rg_tick_launch_p<decltype(p)::value>(); });
+}
 
 
 // (rg_create's failure paths and rg_destroy)
@@ -149,6 +153,7 @@ extern "C" int rg_create(const rg_config *cfg, rg_engine **out) try {
     h->cfg = *cfg;
     h->G = cfg->n_groups;
     h->P = cfg->n_slots;
+    h->launch = &rg_tick_launch(h->P);
     h->stride = (h->G + 255) / 256 * 256;
     h->stream = nullptr;
     h->ckpt = nullptr;

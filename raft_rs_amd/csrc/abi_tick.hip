@@ -8,6 +8,38 @@
 // ------------------------------------------------------------------------------------------------
 
 
+// Is the engine's stream being captured into a graph? on_error: the answer when the query itself fails.
+static bool rg_capturing(rg_engine *h, bool on_error) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess) return on_error;
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// The reduction over RG_COL_OUT (k_count_out), waited for: c[0] groups whose tick changed something, c[1] groups with a fault,
+// c[2] groups that carry RG_OUT_HOST_HINT.
+static int rg_count_out(rg_engine *h, u64 c[3]) {
+    c[0] = c[1] = c[2] = 0;
+    RG_HIP(hipMemsetAsync(h->d_counts, 0, 32, h->stream));
+    const unsigned grid = rg_grid(h->G, RG_BLOCK) < 2048 ? rg_grid(h->G, RG_BLOCK) : 2048;
+    hipLaunchKernelGGL(k_count_out, dim3(grid), dim3(RG_BLOCK), 0, h->stream, (const u32 *)h->st.out, h->G, h->d_counts);
+    RG_HIP(hipMemcpyAsync(c, h->d_counts, 24, hipMemcpyDeviceToHost, h->stream));
+    RG_HIP(hipStreamSynchronize(h->stream));
+    return RG_OK;
+}
+
+// The caller's message columns as the kernels take them: an absent hint / request-snapshot / log-term column reads as zeros.
+static RgMsgs rg_msgs_view(const rg_engine *h, const rg_msgs &m) {
+    RgMsgs ms;
+    ms.mi = (const u64 *)m.m_index;
+    ms.mc = (const u64 *)m.m_commit;
+    ms.mh = m.m_hint ? (const u64 *)m.m_hint : h->zero_col;
+    ms.mrs = m.m_rs ? (const u64 *)m.m_rs : h->zero_col;
+    ms.mlt = m.m_logterm ? (const u64 *)m.m_logterm : h->zero_col;
+    ms.mflags = (const u64 *)m.m_flags;
+    ms.mhr = ms.mh;
+    return ms;
+}
+
 // Device Inflights: a tick's result word carries free_to / free_first_one / left-Replicate effects for the rings. If
 // the host skipped rg_send_appends, apply those effects (and nothing else: the send requests are dropped, which
 // is what skipping the stage means) before the next tick overwrites RG_COL_OUT, so no window is left stale.
@@ -30,12 +62,9 @@ int rg_require_hints_resolved(rg_engine *h, const char *who) {
             return RG_OK;
         }
     }
-    RG_HIP(hipMemsetAsync(h->d_counts, 0, 32, h->stream));
-    const unsigned grid = rg_grid(h->G, RG_BLOCK) < 2048 ? rg_grid(h->G, RG_BLOCK) : 2048;
-    hipLaunchKernelGGL(k_count_out, dim3(grid), dim3(RG_BLOCK), 0, h->stream, (const u32 *)h->st.out, h->G, h->d_counts);
-    u64 c[3] = {0, 0, 0};
-    RG_HIP(hipMemcpyAsync(c, h->d_counts, 24, hipMemcpyDeviceToHost, h->stream));
-    RG_HIP(hipStreamSynchronize(h->stream));
+    u64 c[3];
+    const int crc = rg_count_out(h, c);
+    if (crc) return crc;
     if (c[2])
         return rg_fail(RG_ERR_STATE, "%s: %llu group(s) still carry RG_OUT_HOST_HINT; with device Inflights (max_inflight > 0) "
                                      "rg_resolve_host_hints must answer every hint before the next step (rg_host_hints lists them)",
@@ -51,10 +80,7 @@ int rg_require_hints_resolved(rg_engine *h, const char *who) {
 // a captured launch sequence is replayed without the host, which could neither wait for the event nor read the word): such a tick
 // falls back to what round 5 did -- the counting check at the next entry point / no stop inside a fused call.
 static int rg_hint_prepass(rg_engine *h, RgMsgs &ms, bool probe, bool *probed = nullptr) {
-    if (probe) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) probe = false;
-    }
+    if (probe && rg_capturing(h, true)) probe = false;
     if (probed) *probed = probe;
     if (probe) {
         if (!h->pin_hint_raised) {
@@ -128,32 +154,99 @@ int rg_refresh_classes(rg_engine *h) {
     return RG_OK;
 }
 
+// The engine runs the lane kernels: every variant but the LDS-staged and the compacting comparison kernels.
+static bool rg_lane_variant(const rg_engine *h) {
+    return h->cfg.variant != RG_VARIANT_LDS && h->cfg.variant != RG_VARIANT_LDS_DMA && h->cfg.variant != RG_VARIANT_COMPACT;
+}
+
+// What a dense tick will run, decided before anything is launched: the kernel (RG_KERNEL_*), the width of its cell offsets and
+// its memory regime (0 = cached, 1 = message columns streamed, 2 = state columns as well) -- what rg_device_info reports.
+struct RgTickPlan {
+    u32 kernel, offset_bits, streaming;
+};
+
+static int rg_plan_tick(rg_engine *h, bool send, RgTickPlan *plan) {
+    const bool ix32 = rg_ix32(h->st, h->P), gc = h->any_group_commit, lane = rg_lane_variant(h);
+    const u32 ntm = h->nt_all ? 2u : h->nt_msgs ? 1u : 0u;
+    if (send) { // (k_tick_send streams its message columns at any size; the one all-streamed instantiation: rg_launch_tick_send_t)
+        *plan = {RG_KERNEL_TICK_SEND, ix32 ? 32u : 64u, (h->nt_all && !gc && ix32) ? 2u : 1u};
+        return RG_OK;
+    }
+    // a class-placed shard (replica sets of different sizes in contiguous ranges): ONE launch whose blocks run the tick
+    // instantiated for the slots their groups have (k_tick_classes). Lane variant, no group commit, 32-bit cell offsets.
+    if (lane && !gc && h->P >= 4 && !h->cls_off && ix32) {
+        // (the refresh synchronises: not inside a stream capture -- a captured tick of a stale engine takes the plain kernel)
+        if (h->cls_stale && !rg_capturing(h, false)) {
+            const int crc = rg_refresh_classes(h);
+            if (crc) return crc;
+        }
+        if (h->cls_on && !h->cls_stale) {
+            *plan = {RG_KERNEL_CLASSES, 32u, ntm}; // (the class bodies exist for 32-bit offsets only: the condition above)
+            return RG_OK;
+        }
+    }
+    u32 kernel = lane ? RG_KERNEL_LANE : h->cfg.variant == RG_VARIANT_COMPACT ? RG_KERNEL_COMPACT : RG_KERNEL_LDS;
+    if (h->nt_resident && kernel == RG_KERNEL_LANE && !gc && ix32) kernel = RG_KERNEL_SPLIT;
+    // (the LDS-staged comparison kernels index with 64 bits at any size; the group-commit instantiation and the LDS / compact
+    // variants have no streaming twins: rg_launch_tick_gc)
+    *plan = {kernel, (kernel != RG_KERNEL_LDS && ix32) ? 32u : 64u,
+             kernel == RG_KERNEL_SPLIT ? 2u : (kernel == RG_KERNEL_LANE && !gc) ? ntm : 0u};
+    return RG_OK;
+}
+
+static void rg_after_dense_tick(rg_engine *h, const RgTickPlan &plan) {
+    h->dev.last_tick_kernel = plan.kernel;
+    h->dev.last_tick_offset_bits = plan.offset_bits;
+    h->dev.last_tick_streaming = plan.streaming;
+    h->tick_launches++;
+    h->ticked = true;
+    h->out_is_dense = true;
+    h->send_ready = true;
+    h->host_res_valid = false;
+}
+
 // `send` != NULL: the tick and its send stage as ONE launch (k_tick_send; rg_tick_send / rg_tick_device_send)
 int rg_tick_impl(rg_engine *h, const RgMsgs &ms, const RgSendReq *send) {
     int src = rg_settle_send(h);
     if (src) return src;
-    if (send) {
-        const bool nts = h->nt_all && !h->any_group_commit && rg_ix32(h->st, h->P);
-        switch (h->P) {
-        case 1: rg_launch_tick_send_t<1>(h->stream, h->st, ms, h->any_group_commit, h->ins, send->max_entries, send->flags, h->send_cols, nts); break;
-        case 2: rg_launch_tick_send_t<2>(h->stream, h->st, ms, h->any_group_commit, h->ins, send->max_entries, send->flags, h->send_cols, nts); break;
-        case 3: rg_launch_tick_send_t<3>(h->stream, h->st, ms, h->any_group_commit, h->ins, send->max_entries, send->flags, h->send_cols, nts); break;
-        case 4: rg_launch_tick_send_t<4>(h->stream, h->st, ms, h->any_group_commit, h->ins, send->max_entries, send->flags, h->send_cols, nts); break;
-        case 5: rg_launch_tick_send_t<5>(h->stream, h->st, ms, h->any_group_commit, h->ins, send->max_entries, send->flags, h->send_cols, nts); break;
-        case 6: rg_launch_tick_send_t<6>(h->stream, h->st, ms, h->any_group_commit, h->ins, send->max_entries, send->flags, h->send_cols, nts); break;
-        case 7: rg_launch_tick_send_t<7>(h->stream, h->st, ms, h->any_group_commit, h->ins, send->max_entries, send->flags, h->send_cols, nts); break;
-        default: rg_launch_tick_send_t<8>(h->stream, h->st, ms, h->any_group_commit, h->ins, send->max_entries, send->flags, h->send_cols, nts); break;
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "tick + send stage launch failed: %s", hipGetErrorString(e));
-        h->dev.last_tick_kernel = RG_KERNEL_TICK_SEND;
-        h->dev.last_tick_offset_bits = rg_ix32(h->st, h->P) ? 32u : 64u;
-        h->dev.last_tick_streaming = nts ? 2u : 1u; // (k_tick_send streams its message columns at any size)
-        h->tick_launches++;
-        h->ticked = true;
-        h->out_is_dense = true;
-        h->host_res_valid = false;
-        // what rg_send_appends leaves behind a dense stage
+    // commit publication: the event rg_publish_commit would record behind this tick rides on the tick's own dispatch packet
+    // (RG_LAUNCH_TICK, rg_tick_kernels.h) -- not while the stream is being captured into a graph, not for the ranks of
+    // rg_comm_init_all (their publication records its events itself), not with a send stage in the launch
+    int evt_slot = -1;
+#ifndef RG_NO_PUB_RIDE /* (measurement builds: python -m raft_rs_amd.build --exp noride -DRG_NO_PUB_RIDE) */
+    if (!send && h->pub && !h->pub->in_process && !rg_capturing(h, true)) evt_slot = (int)(h->pub->n_pub % RG_PUB_SEND);
+#endif
+    const hipEvent_t stop_evt = evt_slot >= 0 ? h->pub->ev_tick[evt_slot] : nullptr;
+    RgTickPlan plan;
+    const int prc = rg_plan_tick(h, send != nullptr, &plan);
+    if (prc) return prc;
+    // one table of launchers per slot count (tick_inst.hip, -DRG_P=n); the group-commit kernel is only needed when some group
+    // has ProgressTracker.group_commit set
+    const RgTickLaunch &go = *h->launch;
+    const bool gc = h->any_group_commit;
+    bool rode = false; // the event went out with the launch
+    switch (plan.kernel) {
+    case RG_KERNEL_TICK_SEND:
+        go.tick_send(h->stream, h->st, ms, gc, h->ins, send->max_entries, send->flags, h->send_cols, plan.streaming == 2u);
+        break;
+    case RG_KERNEL_CLASSES: {
+        RgClasses cls;
+        cls.order = h->cls_order;
+        rode = go.classes(h->stream, h->st, ms, (int)plan.streaming, cls, stop_evt);
+        break;
+    }
+    case RG_KERNEL_SPLIT: rode = go.split(h->stream, h->st, ms, h->nt_resident, stop_evt); break;
+    default: { // the lane kernel in the engine's memory regime, or the comparison kernel the engine was created with
+        const u32 variant = rg_lane_variant(h) ? (u32)RG_VARIANT_LANE : (u32)h->cfg.variant;
+        rode = go.tick(h->stream, h->st, ms, variant | (h->nt_msgs ? RG_VARIANT_NT_MSGS : 0u) | (h->nt_all ? RG_VARIANT_NT_ALL : 0u), gc, stop_evt);
+        break;
+    }
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, send ? "tick + send stage launch failed: %s" : "tick launch failed: %s", hipGetErrorString(e));
+    if (rode) h->pub_tick_evt = evt_slot;
+    rg_after_dense_tick(h, plan);
+    if (send) { // what rg_send_appends leaves behind a dense stage
         h->stage_max_entries = send->max_entries;
         h->stage_flags = send->flags;
         h->send_ready = false;
@@ -161,102 +254,7 @@ int rg_tick_impl(rg_engine *h, const RgMsgs &ms, const RgSendReq *send) {
         h->send_cols_fresh = true;
         h->send_last_dense = true;
         h->host_items_valid = false;
-        return RG_OK;
     }
-    // commit publication: the event rg_publish_commit would record behind this tick rides on the tick's own dispatch packet
-    // (RG_LAUNCH_TICK, rg_tick_kernels.h) -- not while the stream is being captured into a graph, not for the ranks of
-    // rg_comm_init_all (their publication records its events itself)
-    int evt_slot = -1;
-#ifndef RG_NO_PUB_RIDE /* (measurement builds: python -m raft_rs_amd.build --exp noride -DRG_NO_PUB_RIDE) */
-    if (h->pub && !h->pub->in_process) {
-        hipStreamCaptureStatus pcs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &pcs) == hipSuccess && pcs == hipStreamCaptureStatusNone) evt_slot = (int)(h->pub->n_pub % RG_PUB_SEND);
-    }
-#endif
-    struct RgStopEvt { // (armed for the launches of THIS call only, whatever way it returns)
-        explicit RgStopEvt(hipEvent_t e) { rg_tls_stop_event = e; }
-        ~RgStopEvt() { rg_tls_stop_event = nullptr; }
-        bool went_out() const { return rg_tls_stop_event == nullptr; }
-    } stop_evt(evt_slot >= 0 ? h->pub->ev_tick[evt_slot] : nullptr);
-    // one translation unit per slot count (tick_inst.hip, -DRG_P=n); the group-commit kernel is only
-    // needed when some group has ProgressTracker.group_commit set
-    const u32 variant = ((h->cfg.variant == RG_VARIANT_LDS || h->cfg.variant == RG_VARIANT_LDS_DMA || h->cfg.variant == RG_VARIANT_COMPACT)
-                             ? h->cfg.variant : RG_VARIANT_LANE) | (h->nt_msgs ? RG_VARIANT_NT_MSGS : 0u) | (h->nt_all ? RG_VARIANT_NT_ALL : 0u);
-    // a class-placed shard (replica sets of different sizes in contiguous ranges): ONE launch whose blocks run the tick
-    // instantiated for the slots their groups have (k_tick_classes). Lane variant, no group commit, 32-bit cell offsets.
-    if ((variant & ~(RG_VARIANT_NT_MSGS | RG_VARIANT_NT_ALL)) == RG_VARIANT_LANE && !h->any_group_commit && h->P >= 4 && !h->cls_off && rg_ix32(h->st, h->P)) {
-        if (h->cls_stale) {
-            // (the refresh synchronises: not inside a stream capture -- a captured tick of a stale engine takes the plain kernel)
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(h->stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
-            if (cs == hipStreamCaptureStatusNone) {
-                const int crc = rg_refresh_classes(h);
-                if (crc) return crc;
-            }
-        }
-        if (h->cls_on && !h->cls_stale) {
-            RgClasses cls;
-            cls.order = h->cls_order;
-            switch (h->P) {
-            case 4: rg_launch_tick_classes_t<4>(h->stream, h->st, ms, h->nt_all ? 2 : h->nt_msgs ? 1 : 0, cls); break;
-            case 5: rg_launch_tick_classes_t<5>(h->stream, h->st, ms, h->nt_all ? 2 : h->nt_msgs ? 1 : 0, cls); break;
-            case 6: rg_launch_tick_classes_t<6>(h->stream, h->st, ms, h->nt_all ? 2 : h->nt_msgs ? 1 : 0, cls); break;
-            case 7: rg_launch_tick_classes_t<7>(h->stream, h->st, ms, h->nt_all ? 2 : h->nt_msgs ? 1 : 0, cls); break;
-            default: rg_launch_tick_classes_t<8>(h->stream, h->st, ms, h->nt_all ? 2 : h->nt_msgs ? 1 : 0, cls); break;
-            }
-            hipError_t ce = hipGetLastError();
-            if (ce != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "tick launch failed: %s", hipGetErrorString(ce));
-            if (evt_slot >= 0 && stop_evt.went_out()) h->pub_tick_evt = evt_slot;
-            h->dev.last_tick_kernel = RG_KERNEL_CLASSES;
-            h->dev.last_tick_offset_bits = 32u; // (the class bodies exist for 32-bit offsets only: the condition above)
-            h->dev.last_tick_streaming = h->nt_all ? 2u : h->nt_msgs ? 1u : 0u;
-            h->tick_launches++;
-            h->ticked = true;
-            h->out_is_dense = true;
-            h->send_ready = true;
-            h->host_res_valid = false;
-            return RG_OK;
-        }
-    }
-    u32 kernel = (variant & ~(RG_VARIANT_NT_MSGS | RG_VARIANT_NT_ALL)) == RG_VARIANT_LANE ? RG_KERNEL_LANE
-                 : (variant & 0xffu) == RG_VARIANT_COMPACT                                 ? RG_KERNEL_COMPACT
-                                                                                           : RG_KERNEL_LDS;
-    if (h->nt_resident && kernel == RG_KERNEL_LANE && !h->any_group_commit && rg_ix32(h->st, h->P)) {
-        kernel = RG_KERNEL_SPLIT;
-        switch (h->P) {
-        case 1: rg_launch_tick_split_t<1>(h->stream, h->st, ms, h->nt_resident); break;
-        case 2: rg_launch_tick_split_t<2>(h->stream, h->st, ms, h->nt_resident); break;
-        case 3: rg_launch_tick_split_t<3>(h->stream, h->st, ms, h->nt_resident); break;
-        case 4: rg_launch_tick_split_t<4>(h->stream, h->st, ms, h->nt_resident); break;
-        case 5: rg_launch_tick_split_t<5>(h->stream, h->st, ms, h->nt_resident); break;
-        case 6: rg_launch_tick_split_t<6>(h->stream, h->st, ms, h->nt_resident); break;
-        case 7: rg_launch_tick_split_t<7>(h->stream, h->st, ms, h->nt_resident); break;
-        default: rg_launch_tick_split_t<8>(h->stream, h->st, ms, h->nt_resident); break;
-        }
-    } else
-    switch (h->P) {
-    case 1: rg_launch_tick_t<1>(h->stream, h->st, ms, variant, h->any_group_commit); break;
-    case 2: rg_launch_tick_t<2>(h->stream, h->st, ms, variant, h->any_group_commit); break;
-    case 3: rg_launch_tick_t<3>(h->stream, h->st, ms, variant, h->any_group_commit); break;
-    case 4: rg_launch_tick_t<4>(h->stream, h->st, ms, variant, h->any_group_commit); break;
-    case 5: rg_launch_tick_t<5>(h->stream, h->st, ms, variant, h->any_group_commit); break;
-    case 6: rg_launch_tick_t<6>(h->stream, h->st, ms, variant, h->any_group_commit); break;
-    case 7: rg_launch_tick_t<7>(h->stream, h->st, ms, variant, h->any_group_commit); break;
-    default: rg_launch_tick_t<8>(h->stream, h->st, ms, variant, h->any_group_commit); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "tick launch failed: %s", hipGetErrorString(e));
-    if (evt_slot >= 0 && stop_evt.went_out()) h->pub_tick_evt = evt_slot;
-    h->dev.last_tick_kernel = kernel;
-    h->dev.last_tick_offset_bits = rg_ix32(h->st, h->P) ? 32u : 64u;
-    if (kernel == RG_KERNEL_LDS) h->dev.last_tick_offset_bits = 64u; // (the LDS-staged comparison kernels index with 64 bits at any size)
-    // (the group-commit instantiation and the LDS / compact variants have no streaming twins: rg_launch_tick_gc)
-    h->dev.last_tick_streaming = kernel == RG_KERNEL_SPLIT ? 2u : (kernel == RG_KERNEL_LANE && !h->any_group_commit) ? (h->nt_all ? 2u : h->nt_msgs ? 1u : 0u) : 0u;
-    h->tick_launches++;
-    h->ticked = true;
-    h->out_is_dense = true;
-    h->send_ready = true;
-    h->host_res_valid = false;
     return RG_OK;
 }
 
@@ -268,8 +266,7 @@ extern "C" int rg_size_classes(rg_engine *h, rg_size_class *out, uint32_t cap, u
         const int rc = rg_refresh_classes(h);
         if (rc) return rc;
     }
-    const bool usable = (h->cfg.variant != RG_VARIANT_LDS && h->cfg.variant != RG_VARIANT_LDS_DMA && h->cfg.variant != RG_VARIANT_COMPACT) &&
-                        !h->any_group_commit && !h->cls_off && rg_ix32(h->st, h->P);
+    const bool usable = rg_lane_variant(h) && !h->any_group_commit && !h->cls_off && rg_ix32(h->st, h->P);
     if (!usable) return RG_OK;
     if (!h->cls_on) return RG_OK;
     u32 k = 0; // run-length encode the per-block bytes
@@ -297,75 +294,54 @@ int rg_send_check(rg_engine *h, uint32_t flags, const char *who) {
     return RG_OK;
 }
 
-static int rg_tick_device_impl(rg_engine *h, const rg_msgs *m, const RgSendReq *send) {
-    RG_ENTER(h);
-    {   // (device Inflights: nothing of the next step is enqueued while a host hint of the last one is unanswered)
-        const int hrc__ = rg_require_hints_resolved(h, "rg_tick_device");
-        if (hrc__) return hrc__;
-    }
-    RgMsgs ms;
-    ms.mi = (const u64 *)m->m_index;
-    ms.mc = (const u64 *)m->m_commit;
-    ms.mh = m->m_hint ? (const u64 *)m->m_hint : h->zero_col;
-    ms.mrs = m->m_rs ? (const u64 *)m->m_rs : h->zero_col;
-    ms.mlt = m->m_logterm ? (const u64 *)m->m_logterm : h->zero_col;
-    ms.mflags = (const u64 *)m->m_flags;
-    ms.mhr = ms.mh;
+// The pre-pass of a tick whose messages carry a log-term column, the tick, and what rg_require_hints_resolved has to know of it
+static int rg_tick_msgs(rg_engine *h, RgMsgs &ms, bool logterm, const RgSendReq *send) {
     bool probed = false;
-    if (m->m_logterm) { // this tick may carry log terms: resolve the flagged hints first
+    if (logterm) { // this tick may carry log terms: resolve the flagged hints first (find_conflict_by_term)
         const int prc = rg_hint_prepass(h, ms, h->ins_arena != nullptr, &probed);
         if (prc) return prc;
     }
     const int trc = rg_tick_impl(h, ms, send);
-    if (trc == RG_OK && m->m_logterm && h->ins_arena) { // (rg_require_hints_resolved: this tick CAN have raised RG_OUT_HOST_HINT;
-        h->hint_check_due = true;                       //  whether it did is in the probe's word, read at the next entry point)
+    if (trc == RG_OK && logterm && h->ins_arena) { // (rg_require_hints_resolved: this tick CAN have raised RG_OUT_HOST_HINT;
+        h->hint_check_due = true;                  //  whether it did is in the probe's word, read at the next entry point)
         h->hint_probe_pending = probed;
     }
     return trc;
 }
 
-extern "C" int rg_tick_device(rg_engine *h, const rg_msgs *m) try {
+static int rg_tick_device_impl(rg_engine *h, const rg_msgs *m, const RgSendReq *send) {
+    RG_ENTER_STEP(h, "rg_tick_device");
+    RgMsgs ms = rg_msgs_view(h, *m);
+    return rg_tick_msgs(h, ms, m->m_logterm != nullptr, send);
+}
+
+// The argument check of the four tick entry points; those with a send stage in the launch (`send`) add rg_send_check's
+static int rg_tick_args(rg_engine *h, const rg_msgs *m, const RgSendReq *send, const char *who) {
     if (!h || !m || !m->m_index || !m->m_commit || !m->m_flags)
-        return rg_fail(RG_ERR_INVALID_ARG, "rg_tick_device: m_index, m_commit and m_flags are required");
-    return rg_tick_device_impl(h, m, nullptr);
+        return rg_fail(RG_ERR_INVALID_ARG, "%s: m_index, m_commit and m_flags are required", who);
+    return send ? rg_send_check(h, send->flags, who) : RG_OK;
+}
+
+extern "C" int rg_tick_device(rg_engine *h, const rg_msgs *m) try {
+    const int rc = rg_tick_args(h, m, nullptr, "rg_tick_device");
+    return rc ? rc : rg_tick_device_impl(h, m, nullptr);
 } RG_ABI_GUARD
 
 extern "C" int rg_tick_device_send(rg_engine *h, const rg_msgs *m, uint64_t max_entries_per_msg, uint32_t flags) try {
-    if (!h || !m || !m->m_index || !m->m_commit || !m->m_flags)
-        return rg_fail(RG_ERR_INVALID_ARG, "rg_tick_device_send: m_index, m_commit and m_flags are required");
-    int rc = rg_send_check(h, flags, "rg_tick_device_send");
-    if (rc) return rc;
     const RgSendReq send = {(u64)max_entries_per_msg, (u32)flags};
-    return rg_tick_device_impl(h, m, &send);
+    const int rc = rg_tick_args(h, m, &send, "rg_tick_device_send");
+    return rc ? rc : rg_tick_device_impl(h, m, &send);
 } RG_ABI_GUARD
 
 // One fused launch over ticks [t0, t0 + n) of the caller's array (none of them carries Message.log_term).
 static int rg_fused_run(rg_engine *h, const rg_msgs *m, u32 t0, u32 n, uint32_t *dev_out_t, uint64_t *dev_commit_t) {
     RgFused fm;
     memset(&fm, 0, sizeof(fm));
-    for (u32 i = 0; i < n; i++) {
-        const rg_msgs &x = m[t0 + i];
-        fm.m[i].mi = (const u64 *)x.m_index;
-        fm.m[i].mc = (const u64 *)x.m_commit;
-        fm.m[i].mh = x.m_hint ? (const u64 *)x.m_hint : h->zero_col;
-        fm.m[i].mrs = x.m_rs ? (const u64 *)x.m_rs : h->zero_col;
-        fm.m[i].mlt = h->zero_col;
-        fm.m[i].mhr = fm.m[i].mh;
-        fm.m[i].mflags = (const u64 *)x.m_flags;
-    }
+    for (u32 i = 0; i < n; i++) fm.m[i] = rg_msgs_view(h, m[t0 + i]);
     fm.out_t = dev_out_t + (size_t)t0 * h->G;
     fm.commit_t = dev_commit_t ? (u64 *)dev_commit_t + (size_t)t0 * h->G : nullptr;
     fm.n_ticks = n;
-    switch (h->P) {
-    case 1: rg_launch_tick_fused_t<1>(h->stream, h->st, fm, h->any_group_commit); break;
-    case 2: rg_launch_tick_fused_t<2>(h->stream, h->st, fm, h->any_group_commit); break;
-    case 3: rg_launch_tick_fused_t<3>(h->stream, h->st, fm, h->any_group_commit); break;
-    case 4: rg_launch_tick_fused_t<4>(h->stream, h->st, fm, h->any_group_commit); break;
-    case 5: rg_launch_tick_fused_t<5>(h->stream, h->st, fm, h->any_group_commit); break;
-    case 6: rg_launch_tick_fused_t<6>(h->stream, h->st, fm, h->any_group_commit); break;
-    case 7: rg_launch_tick_fused_t<7>(h->stream, h->st, fm, h->any_group_commit); break;
-    default: rg_launch_tick_fused_t<8>(h->stream, h->st, fm, h->any_group_commit); break;
-    }
+    h->launch->fused(h->stream, h->st, fm, h->any_group_commit);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "fused tick launch failed: %s", hipGetErrorString(e));
     return RG_OK;
@@ -399,14 +375,7 @@ extern "C" int rg_tick_device_fused(rg_engine *h, const rg_msgs *m, uint32_t n_t
             if (rc) return rc;
         }
         if (e < n_ticks) {
-            RgMsgs ms;
-            ms.mi = (const u64 *)m[e].m_index;
-            ms.mc = (const u64 *)m[e].m_commit;
-            ms.mh = m[e].m_hint ? (const u64 *)m[e].m_hint : h->zero_col;
-            ms.mrs = m[e].m_rs ? (const u64 *)m[e].m_rs : h->zero_col;
-            ms.mlt = (const u64 *)m[e].m_logterm;
-            ms.mflags = (const u64 *)m[e].m_flags;
-            ms.mhr = ms.mh;
+            RgMsgs ms = rg_msgs_view(h, m[e]);
             bool probed = false;
             int rc = rg_hint_prepass(h, ms, true, &probed);
             if (rc) return rc;
@@ -423,12 +392,9 @@ extern "C" int rg_tick_device_fused(rg_engine *h, const rg_msgs *m, uint32_t n_t
             // pre-pass's word says "none" without waiting for the tick; only a raised word costs the count and its wait.
             if (probed) RG_HIP(hipEventSynchronize(h->ev_hint));
             if (probed && e < n_ticks && *(volatile u32 *)h->pin_hint_raised != 0) {
-                RG_HIP(hipMemsetAsync(h->d_counts, 0, 32, h->stream));
-                const unsigned grid = rg_grid(h->G, RG_BLOCK) < 2048 ? rg_grid(h->G, RG_BLOCK) : 2048;
-                hipLaunchKernelGGL(k_count_out, dim3(grid), dim3(RG_BLOCK), 0, h->stream, (const u32 *)h->st.out, h->G, h->d_counts);
-                u64 c[3] = {0, 0, 0};
-                RG_HIP(hipMemcpyAsync(c, h->d_counts, 24, hipMemcpyDeviceToHost, h->stream));
-                RG_HIP(hipStreamSynchronize(h->stream));
+                u64 c[3];
+                rc = rg_count_out(h, c);
+                if (rc) return rc;
                 if (c[2]) {
                     h->ticked = true;
                     h->host_res_valid = false;
@@ -470,15 +436,10 @@ int rg_ensure_msg_arena(rg_engine *h) {
 }
 
 int rg_tick_host_impl(rg_engine *h, const rg_msgs *m, const RgSendReq *send) {
-    RG_ENTER(h);
-    {   // (device Inflights: nothing of the next step is enqueued while a host hint of the last one is unanswered)
-        const int hrc__ = rg_require_hints_resolved(h, "rg_tick");
-        if (hrc__) return hrc__;
-    }
+    RG_ENTER_STEP(h, "rg_tick");
     int rc = rg_ensure_msg_arena(h);
     if (rc) return rc;
     const size_t colb = (size_t)h->P * h->stride * 8;
-    bool probed = false;
     RG_HIP(hipMemcpyAsync((void *)h->staged.mi, m->m_index, colb, hipMemcpyHostToDevice, h->stream));
     RG_HIP(hipMemcpyAsync((void *)h->staged.mc, m->m_commit, colb, hipMemcpyHostToDevice, h->stream));
     RgMsgs ms = h->staged;
@@ -490,16 +451,8 @@ int rg_tick_host_impl(rg_engine *h, const rg_msgs *m, const RgSendReq *send) {
     if (m->m_logterm) RG_HIP(hipMemcpyAsync((void *)h->staged.mlt, m->m_logterm, colb, hipMemcpyHostToDevice, h->stream));
     else ms.mlt = h->zero_col;
     RG_HIP(hipMemcpyAsync((void *)h->staged.mflags, m->m_flags, h->G * 8, hipMemcpyHostToDevice, h->stream));
-    if (m->m_logterm) { // pre-pass (after ALL message columns are on the device): find_conflict_by_term
-        rc = rg_hint_prepass(h, ms, h->ins_arena != nullptr, &probed);
-        if (rc) return rc;
-    }
-    rc = rg_tick_impl(h, ms, send);
+    rc = rg_tick_msgs(h, ms, m->m_logterm != nullptr, send); // (the pre-pass comes after ALL message columns are on the device)
     if (rc) return rc;
-    if (m->m_logterm && h->ins_arena) {
-        h->hint_check_due = true;
-        h->hint_probe_pending = probed;
-    }
     // the engine-owned message columns must read "no events" outside a tick (sparse-path invariant)
     RG_HIP(hipMemsetAsync((void *)h->staged.mflags, 0, h->stride * 8, h->stream));
     RG_HIP(hipStreamSynchronize(h->stream)); // caller-owned host buffers may be reused after return
@@ -507,18 +460,14 @@ int rg_tick_host_impl(rg_engine *h, const rg_msgs *m, const RgSendReq *send) {
 }
 
 extern "C" int rg_tick(rg_engine *h, const rg_msgs *m) try {
-    if (!h || !m || !m->m_index || !m->m_commit || !m->m_flags)
-        return rg_fail(RG_ERR_INVALID_ARG, "rg_tick: m_index, m_commit and m_flags are required");
-    return rg_tick_host_impl(h, m, nullptr);
+    const int rc = rg_tick_args(h, m, nullptr, "rg_tick");
+    return rc ? rc : rg_tick_host_impl(h, m, nullptr);
 } RG_ABI_GUARD
 
 extern "C" int rg_tick_send(rg_engine *h, const rg_msgs *m, uint64_t max_entries_per_msg, uint32_t flags) try {
-    if (!h || !m || !m->m_index || !m->m_commit || !m->m_flags)
-        return rg_fail(RG_ERR_INVALID_ARG, "rg_tick_send: m_index, m_commit and m_flags are required");
-    int rc = rg_send_check(h, flags, "rg_tick_send");
-    if (rc) return rc;
     const RgSendReq send = {(u64)max_entries_per_msg, (u32)flags};
-    return rg_tick_host_impl(h, m, &send);
+    const int rc = rg_tick_args(h, m, &send, "rg_tick_send");
+    return rc ? rc : rg_tick_host_impl(h, m, &send);
 } RG_ABI_GUARD
 
 
@@ -543,16 +492,7 @@ template <bool COMMIT> static int rg_recompute_impl(rg_engine *h, u64 *mci, u8 *
         return RG_OK;
     }
     const bool x2 = RG_RECOMPUTE_X2 && h->cfg.variant != RG_VARIANT_LANE; // (variant LANE pins one group per lane)
-    switch (h->P) {
-    case 1: rg_launch_recompute_p<1, COMMIT>(h, mci, gc, x2); break;
-    case 2: rg_launch_recompute_p<2, COMMIT>(h, mci, gc, x2); break;
-    case 3: rg_launch_recompute_p<3, COMMIT>(h, mci, gc, x2); break;
-    case 4: rg_launch_recompute_p<4, COMMIT>(h, mci, gc, x2); break;
-    case 5: rg_launch_recompute_p<5, COMMIT>(h, mci, gc, x2); break;
-    case 6: rg_launch_recompute_p<6, COMMIT>(h, mci, gc, x2); break;
-    case 7: rg_launch_recompute_p<7, COMMIT>(h, mci, gc, x2); break;
-    default: rg_launch_recompute_p<8, COMMIT>(h, mci, gc, x2); break;
-    }
+    rg_with_p(h->P, [&](auto p) { rg_launch_recompute_p<decltype(p)::value, COMMIT>(h, mci, gc, x2); });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "recompute launch failed: %s", hipGetErrorString(e));
     return RG_OK;
@@ -560,11 +500,7 @@ template <bool COMMIT> static int rg_recompute_impl(rg_engine *h, u64 *mci, u8 *
 
 extern "C" int rg_recompute(rg_engine *h) try {
     if (!h) return rg_fail(RG_ERR_INVALID_ARG, "rg_recompute: null engine");
-    RG_ENTER(h);
-    {   // (device Inflights: nothing of the next step is enqueued while a host hint of the last one is unanswered)
-        const int hrc__ = rg_require_hints_resolved(h, "rg_recompute");
-        if (hrc__) return hrc__;
-    }
+    RG_ENTER_STEP(h, "rg_recompute");
     int rc = rg_settle_send(h);
     if (rc) return rc;
     rc = rg_recompute_impl<true>(h, nullptr, nullptr);
@@ -638,12 +574,9 @@ extern "C" int rg_result_counts(rg_engine *h, uint64_t *n_changed, uint64_t *n_f
     if (!h) return rg_fail(RG_ERR_INVALID_ARG, "rg_result_counts: null engine");
     if (!h->ticked) return rg_fail(RG_ERR_STATE, "rg_result_counts: no tick has run yet");
     RG_ENTER(h);
-    RG_HIP(hipMemsetAsync(h->d_counts, 0, 32, h->stream));
-    const unsigned grid = rg_grid(h->G, RG_BLOCK) < 2048 ? rg_grid(h->G, RG_BLOCK) : 2048;
-    hipLaunchKernelGGL(k_count_out, dim3(grid), dim3(RG_BLOCK), 0, h->stream, (const u32 *)h->st.out, h->G, h->d_counts);
-    u64 c[2] = {0, 0};
-    RG_HIP(hipMemcpyAsync(c, h->d_counts, 16, hipMemcpyDeviceToHost, h->stream));
-    RG_HIP(hipStreamSynchronize(h->stream));
+    u64 c[3];
+    const int rc = rg_count_out(h, c);
+    if (rc) return rc;
     if (n_changed) *n_changed = c[0];
     if (n_fault) *n_fault = c[1];
     return RG_OK;

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <algorithm>
 #include <atomic>
@@ -57,6 +58,29 @@ int rg_require_hints_resolved(rg_engine *h, const char *who); // abi_tick.hip
         int rc__ = rg_mailbox_quiesce(h);                                                          \
         if (rc__) return rc__;                                                                     \
     } while (0)
+// ... and the entry points that start the NEXT step (device Inflights: nothing of it is enqueued while a host hint of the last
+// one is unanswered)
+#define RG_ENTER_STEP(h, who)                                                                      \
+    do {                                                                                           \
+        RG_ENTER(h);                                                                               \
+        const int hrc__ = rg_require_hints_resolved(h, who);                                       \
+        if (hrc__) return hrc__;                                                                   \
+    } while (0)
+
+// The one switch on the slot count: f(std::integral_constant<int, P>{}), for the launches templated on it that live in the ABI
+// units (everything of tick_inst.hip goes through RgTickLaunch instead).
+template <typename F> static inline auto rg_with_p(u32 P, F &&f) {
+    switch (P) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    default: return f(std::integral_constant<int, 8>{});
+    }
+}
 
 // rg_refresh_classes: per block of RG_BLOCK groups (= one workgroup of the lane kernels), the number of slots the block's cfg
 // words name: 1 + the highest slot that is present, a voter of either majority, the leader's own, or the transferee.
@@ -76,6 +100,7 @@ struct rg_engine {
     rg_device_info dev;
     u64 G, stride;
     u32 P;
+    const RgTickLaunch *launch; // the launchers of the kernels instantiated for P slots (rg_tick_launch)
     hipStream_t stream;
     char *arena;      // state columns
     size_t state_bytes;
@@ -89,7 +114,7 @@ struct rg_engine {
     RgState st;
     RgMsgs staged;    // views into msg_arena
     bool ticked;
-    // commit publication: the slot b whose ev_tick[b] rode on the dispatch packet of the LAST dense tick (RG_LAUNCH_TICK), -1 if
+    // commit publication: the slot b whose ev_tick[b] rode on the dispatch packet of the LAST dense tick (rg_tick_impl), -1 if
     // none or if any entry point has run since (RG_ENTER): rg_publish_commit right behind that tick need not record an event
     int pub_tick_evt;
     u64 tick_launches; // ticks enqueued so far (rg_flush: did a failed flush already change device state?)

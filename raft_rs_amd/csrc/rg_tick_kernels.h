@@ -1,6 +1,7 @@
 // rg_tick_kernels.h -- the tick kernels (one lane per raft group; LDS-staged variant) and their
-// launcher. Instantiated once per slot count in tick_inst.hip (-DRG_P=n) so the eight
-// specialisations compile in parallel; the ABI units (abi_*.hip) only see the extern template declarations.
+// launchers. Instantiated once per slot count in tick_inst.hip (-DRG_P=n) so the eight
+// specialisations compile in parallel; the ABI units (abi_*.hip) reach them through one table of launchers per slot
+// count (RgTickLaunch, at the end of this file).
 #pragma once
 
 #include "rg_group.h"
@@ -87,15 +88,11 @@ static inline unsigned rg_grid_for(u64 n, unsigned per_block) { return (unsigned
 // A dense tick's launch can carry an EVENT on its own dispatch packet (hipExtLaunchKernelGGL's stopEvent: the packet's completion
 // signal) instead of a hipEventRecord behind it, which is a barrier packet of its own in the engine's queue and costs the NEXT
 // tick 2.5 us of idle queue (tools/microbench/pub_signal.hip: 51.3 vs 50.1 us per tick, 48.8 without any event). The commit
-// publication uses it (abi_tick.hip sets the thread's pending event around the launch of the lane / class / split kernels;
-// rg_publish_commit then only makes its side stream wait for it).
-inline thread_local hipEvent_t rg_tls_stop_event = nullptr;
-#define RG_LAUNCH_TICK(kernel, grid, block, stream, ...)                                                                          \
+// publication uses it: rg_tick_impl (abi_tick.hip) hands the event to the launchers of the lane / class / split kernels, which
+// say whether it went out; rg_publish_commit then only makes its side stream wait for it. stop_evt may be null.
+#define RG_LAUNCH_TICK(kernel, grid, block, stream, stop_evt, ...)                                                                \
     do {                                                                                                                          \
-        if (rg_tls_stop_event) {                                                                                                  \
-            hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, nullptr, rg_tls_stop_event, 0, __VA_ARGS__);                    \
-            rg_tls_stop_event = nullptr; /* (consumed: the caller sees that the event went out with a launch) */                  \
-        }                                                                                                                         \
+        if (stop_evt) hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, nullptr, stop_evt, 0, __VA_ARGS__);                   \
         else hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);                                                     \
     } while (0)
 
@@ -1229,29 +1226,29 @@ __global__ __launch_bounds__(64 * RG_LDS_WAVES) void k_tick_lds(RgState st, RgMs
 // ------------------------------------------------------------------------------------------------
 #define RG_VARIANT_NT_MSGS 0x100u /* engine-internal flag on the variant word: stream the message columns (k_tick_lane<.., NTM = 1>) */
 #define RG_VARIANT_NT_ALL 0x200u  /* ... and the state columns, loads and stores (NTM = 2): engines far beyond the Infinity Cache */
-template <int P> void rg_launch_tick_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, u32 variant, bool gc);
-// the lane kernel over a class-placed engine (no group commit, 32-bit cell offsets: the caller checks both); P >= 4
-template <int P> void rg_launch_tick_classes_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, int ntm, const RgClasses &cls);
-// the lane kernel with the first resident_blocks workgroups' state kept in the Infinity Cache (no group commit, 32-bit cell offsets)
-template <int P> void rg_launch_tick_split_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, u64 resident_blocks);
-template <int P>
-void rg_launch_tick_list_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const u64 *list,
-                           const u32 *n_ptr, u64 n_upper, u64 *mflags_rw, const RgListOut &lo);
-template <int P> void rg_launch_tick_fused_t(hipStream_t stream, const RgState &st, const RgFused &fm, bool gc);
-template <int P>
-void rg_launch_tick_send_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const RgIns &ins, u64 max_entries,
-                           u32 flags, const RgSendCols &oc, bool nts);
-template <int P>
-void rg_launch_flush_small_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const RgIngest &a, u64 *rh,
-                             u64 *mflags_rw, const RgListOut &lo);
-
-template <int P>
-void rg_launch_mailbox_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const RgIngest &a0, u32 *ctr_base,
-                         u64 *rh, u64 *mflags_rw, const RgListOut &lo, RgMbox *mb, u64 idle_ticks, u64 max_ticks,
-                         const RgSmallSend &ss0);
-template <int P>
-void rg_launch_flush_small_send_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const RgIngest &a, u64 *rh,
-                                  u64 *mflags_rw, const RgListOut &lo, const RgSmallSend &ss);
+// One table of launchers per slot count. tick_inst.hip (-DRG_P=n) fills the table of its slot count from the templates below;
+// rg_tick_launch (abi_state.hip) picks the engine's, once, at rg_create. The three launchers of a dense tick that can carry the
+// publication's event on their dispatch packet take it (stop_evt, may be null) and return whether it went out.
+struct RgTickLaunch {
+    bool (*tick)(hipStream_t stream, const RgState &st, const RgMsgs &ms, u32 variant, bool gc, hipEvent_t stop_evt);
+    // the lane kernel over a class-placed engine (no group commit, 32-bit cell offsets: the caller checks both); a no-op below 4 slots
+    bool (*classes)(hipStream_t stream, const RgState &st, const RgMsgs &ms, int ntm, const RgClasses &cls, hipEvent_t stop_evt);
+    // the lane kernel with the first resident_blocks workgroups' state kept in the Infinity Cache (no group commit, 32-bit cell offsets)
+    bool (*split)(hipStream_t stream, const RgState &st, const RgMsgs &ms, u64 resident_blocks, hipEvent_t stop_evt);
+    void (*list)(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const u64 *list, const u32 *n_ptr, u64 n_upper,
+                 u64 *mflags_rw, const RgListOut &lo);
+    void (*fused)(hipStream_t stream, const RgState &st, const RgFused &fm, bool gc);
+    void (*tick_send)(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const RgIns &ins, u64 max_entries, u32 flags,
+                      const RgSendCols &oc, bool nts);
+    void (*flush_small)(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const RgIngest &a, u64 *rh, u64 *mflags_rw,
+                        const RgListOut &lo);
+    void (*flush_small_send)(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const RgIngest &a, u64 *rh,
+                             u64 *mflags_rw, const RgListOut &lo, const RgSmallSend &ss);
+    void (*mailbox)(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const RgIngest &a0, u32 *ctr_base, u64 *rh,
+                    u64 *mflags_rw, const RgListOut &lo, RgMbox *mb, u64 idle_ticks, u64 max_ticks, const RgSmallSend &ss0);
+};
+template <int P> const RgTickLaunch &rg_tick_launch_p(); // (tick_inst.hip, -DRG_P=P)
+const RgTickLaunch &rg_tick_launch(u32 P);                // (abi_state.hip)
 
 #ifdef RG_TICK_INSTANTIATE
 template <int P>
@@ -1277,13 +1274,13 @@ void rg_launch_flush_small_t(hipStream_t stream, const RgState &st, const RgMsgs
 #define RG_LAUNCH_LANE(IXT)                                                                                                       \
     do {                                                                                                                          \
         if (ntm == 2 && !GC)                                                                                                      \
-            RG_LAUNCH_TICK((k_tick_lane<P, GC, IXT, GC ? 0 : 2>), dim3(rg_grid_for(st.G, RG_BLOCK)), dim3(RG_BLOCK), stream, st, ms); \
+            RG_LAUNCH_TICK((k_tick_lane<P, GC, IXT, GC ? 0 : 2>), dim3(rg_grid_for(st.G, RG_BLOCK)), dim3(RG_BLOCK), stream, stop_evt, st, ms); \
         else if (ntm && !GC)                                                                                                      \
-            RG_LAUNCH_TICK((k_tick_lane<P, GC, IXT, GC ? 0 : 1>), dim3(rg_grid_for(st.G, RG_BLOCK)), dim3(RG_BLOCK), stream, st, ms); \
+            RG_LAUNCH_TICK((k_tick_lane<P, GC, IXT, GC ? 0 : 1>), dim3(rg_grid_for(st.G, RG_BLOCK)), dim3(RG_BLOCK), stream, stop_evt, st, ms); \
         else                                                                                                                      \
-            RG_LAUNCH_TICK((k_tick_lane<P, GC, IXT, 0>), dim3(rg_grid_for(st.G, RG_BLOCK)), dim3(RG_BLOCK), stream, st, ms); \
+            RG_LAUNCH_TICK((k_tick_lane<P, GC, IXT, 0>), dim3(rg_grid_for(st.G, RG_BLOCK)), dim3(RG_BLOCK), stream, stop_evt, st, ms); \
     } while (0)
-template <int P, bool GC> static void rg_launch_tick_gc(hipStream_t stream, const RgState &st, const RgMsgs &ms, u32 variant) {
+template <int P, bool GC> static bool rg_launch_tick_gc(hipStream_t stream, const RgState &st, const RgMsgs &ms, u32 variant, hipEvent_t stop_evt) {
     const int ntm = (variant & RG_VARIANT_NT_ALL) ? 2 : (variant & RG_VARIANT_NT_MSGS) ? 1 : 0;
     variant &= ~(RG_VARIANT_NT_MSGS | RG_VARIANT_NT_ALL);
     if (variant == RG_VARIANT_LDS) {
@@ -1302,13 +1299,15 @@ template <int P, bool GC> static void rg_launch_tick_gc(hipStream_t stream, cons
             RG_LAUNCH_LANE(typename RgLaneIx<P>::type);
         else
             RG_LAUNCH_LANE(u64);
+        return stop_evt != nullptr;
     }
+    return false; // (the LDS-staged and compacting comparison kernels do not take the event)
 }
-template <int P> void rg_launch_tick_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, u32 variant, bool gc) {
-    if (gc) rg_launch_tick_gc<P, true>(stream, st, ms, variant);
-    else rg_launch_tick_gc<P, false>(stream, st, ms, variant);
+template <int P> bool rg_launch_tick_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, u32 variant, bool gc, hipEvent_t stop_evt) {
+    return gc ? rg_launch_tick_gc<P, true>(stream, st, ms, variant, stop_evt) : rg_launch_tick_gc<P, false>(stream, st, ms, variant, stop_evt);
 }
-template <int P> void rg_launch_tick_classes_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, int ntm, const RgClasses &cls) {
+template <int P>
+bool rg_launch_tick_classes_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, int ntm, const RgClasses &cls, hipEvent_t stop_evt) {
     if constexpr (P >= 4) {
         const dim3 grid(rg_grid_for(st.G, RG_BLOCK)), block(RG_BLOCK);
         RgClassArgs a;
@@ -1316,17 +1315,20 @@ template <int P> void rg_launch_tick_classes_t(hipStream_t stream, const RgState
         a.ms = ms;
         a.cls = cls;
         typedef typename RgLaneIx<P>::type IXP;
-        if (ntm == 2) RG_LAUNCH_TICK((k_tick_classes<P, IXP, 2>), grid, block, stream, a);
-        else if (ntm) RG_LAUNCH_TICK((k_tick_classes<P, IXP, 1>), grid, block, stream, a);
-        else RG_LAUNCH_TICK((k_tick_classes<P, IXP, 0>), grid, block, stream, a);
+        if (ntm == 2) RG_LAUNCH_TICK((k_tick_classes<P, IXP, 2>), grid, block, stream, stop_evt, a);
+        else if (ntm) RG_LAUNCH_TICK((k_tick_classes<P, IXP, 1>), grid, block, stream, stop_evt, a);
+        else RG_LAUNCH_TICK((k_tick_classes<P, IXP, 0>), grid, block, stream, stop_evt, a);
+        return stop_evt != nullptr;
     }
+    return false;
 }
-template <int P> void rg_launch_tick_split_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, u64 resident_blocks) {
+template <int P> bool rg_launch_tick_split_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, u64 resident_blocks, hipEvent_t stop_evt) {
     RgSplitArgs a;
     a.st = st;
     a.ms = ms;
     a.resident_blocks = resident_blocks;
-    RG_LAUNCH_TICK((k_tick_split<P, typename RgLaneIx<P>::type>), dim3(rg_grid_for(st.G, RG_BLOCK)), dim3(RG_BLOCK), stream, a);
+    RG_LAUNCH_TICK((k_tick_split<P, typename RgLaneIx<P>::type>), dim3(rg_grid_for(st.G, RG_BLOCK)), dim3(RG_BLOCK), stream, stop_evt, a);
+    return stop_evt != nullptr;
 }
 template <int P>
 void rg_launch_tick_list_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const u64 *list,
@@ -1373,77 +1375,4 @@ void rg_launch_tick_send_t(hipStream_t stream, const RgState &st, const RgMsgs &
         else hipLaunchKernelGGL((k_tick_send<P, false, u64>), grid, block, 0, stream, ta);
     }
 }
-#else
-extern template void rg_launch_tick_t<1>(hipStream_t, const RgState &, const RgMsgs &, u32, bool);
-extern template void rg_launch_tick_classes_t<1>(hipStream_t, const RgState &, const RgMsgs &, int, const RgClasses &);
-extern template void rg_launch_tick_split_t<1>(hipStream_t, const RgState &, const RgMsgs &, u64);
-extern template void rg_launch_tick_list_t<1>(hipStream_t, const RgState &, const RgMsgs &, bool, const u64 *, const u32 *, u64, u64 *, const RgListOut &);
-extern template void rg_launch_tick_fused_t<1>(hipStream_t, const RgState &, const RgFused &, bool);
-extern template void rg_launch_tick_send_t<1>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIns &, u64, u32, const RgSendCols &, bool);
-extern template void rg_launch_flush_small_t<1>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &);
-extern template void rg_launch_flush_small_send_t<1>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &, const RgSmallSend &);
-extern template void rg_launch_mailbox_t<1>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u32 *, u64 *, u64 *, const RgListOut &, RgMbox *, u64, u64, const RgSmallSend &);
-extern template void rg_launch_tick_t<2>(hipStream_t, const RgState &, const RgMsgs &, u32, bool);
-extern template void rg_launch_tick_classes_t<2>(hipStream_t, const RgState &, const RgMsgs &, int, const RgClasses &);
-extern template void rg_launch_tick_split_t<2>(hipStream_t, const RgState &, const RgMsgs &, u64);
-extern template void rg_launch_tick_list_t<2>(hipStream_t, const RgState &, const RgMsgs &, bool, const u64 *, const u32 *, u64, u64 *, const RgListOut &);
-extern template void rg_launch_tick_fused_t<2>(hipStream_t, const RgState &, const RgFused &, bool);
-extern template void rg_launch_tick_send_t<2>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIns &, u64, u32, const RgSendCols &, bool);
-extern template void rg_launch_flush_small_t<2>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &);
-extern template void rg_launch_flush_small_send_t<2>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &, const RgSmallSend &);
-extern template void rg_launch_mailbox_t<2>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u32 *, u64 *, u64 *, const RgListOut &, RgMbox *, u64, u64, const RgSmallSend &);
-extern template void rg_launch_tick_t<3>(hipStream_t, const RgState &, const RgMsgs &, u32, bool);
-extern template void rg_launch_tick_classes_t<3>(hipStream_t, const RgState &, const RgMsgs &, int, const RgClasses &);
-extern template void rg_launch_tick_split_t<3>(hipStream_t, const RgState &, const RgMsgs &, u64);
-extern template void rg_launch_tick_list_t<3>(hipStream_t, const RgState &, const RgMsgs &, bool, const u64 *, const u32 *, u64, u64 *, const RgListOut &);
-extern template void rg_launch_tick_fused_t<3>(hipStream_t, const RgState &, const RgFused &, bool);
-extern template void rg_launch_tick_send_t<3>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIns &, u64, u32, const RgSendCols &, bool);
-extern template void rg_launch_flush_small_t<3>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &);
-extern template void rg_launch_flush_small_send_t<3>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &, const RgSmallSend &);
-extern template void rg_launch_mailbox_t<3>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u32 *, u64 *, u64 *, const RgListOut &, RgMbox *, u64, u64, const RgSmallSend &);
-extern template void rg_launch_tick_t<4>(hipStream_t, const RgState &, const RgMsgs &, u32, bool);
-extern template void rg_launch_tick_classes_t<4>(hipStream_t, const RgState &, const RgMsgs &, int, const RgClasses &);
-extern template void rg_launch_tick_split_t<4>(hipStream_t, const RgState &, const RgMsgs &, u64);
-extern template void rg_launch_tick_list_t<4>(hipStream_t, const RgState &, const RgMsgs &, bool, const u64 *, const u32 *, u64, u64 *, const RgListOut &);
-extern template void rg_launch_tick_fused_t<4>(hipStream_t, const RgState &, const RgFused &, bool);
-extern template void rg_launch_tick_send_t<4>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIns &, u64, u32, const RgSendCols &, bool);
-extern template void rg_launch_flush_small_t<4>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &);
-extern template void rg_launch_flush_small_send_t<4>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &, const RgSmallSend &);
-extern template void rg_launch_mailbox_t<4>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u32 *, u64 *, u64 *, const RgListOut &, RgMbox *, u64, u64, const RgSmallSend &);
-extern template void rg_launch_tick_t<5>(hipStream_t, const RgState &, const RgMsgs &, u32, bool);
-extern template void rg_launch_tick_classes_t<5>(hipStream_t, const RgState &, const RgMsgs &, int, const RgClasses &);
-extern template void rg_launch_tick_split_t<5>(hipStream_t, const RgState &, const RgMsgs &, u64);
-extern template void rg_launch_tick_list_t<5>(hipStream_t, const RgState &, const RgMsgs &, bool, const u64 *, const u32 *, u64, u64 *, const RgListOut &);
-extern template void rg_launch_tick_fused_t<5>(hipStream_t, const RgState &, const RgFused &, bool);
-extern template void rg_launch_tick_send_t<5>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIns &, u64, u32, const RgSendCols &, bool);
-extern template void rg_launch_flush_small_t<5>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &);
-extern template void rg_launch_flush_small_send_t<5>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &, const RgSmallSend &);
-extern template void rg_launch_mailbox_t<5>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u32 *, u64 *, u64 *, const RgListOut &, RgMbox *, u64, u64, const RgSmallSend &);
-extern template void rg_launch_tick_t<6>(hipStream_t, const RgState &, const RgMsgs &, u32, bool);
-extern template void rg_launch_tick_classes_t<6>(hipStream_t, const RgState &, const RgMsgs &, int, const RgClasses &);
-extern template void rg_launch_tick_split_t<6>(hipStream_t, const RgState &, const RgMsgs &, u64);
-extern template void rg_launch_tick_list_t<6>(hipStream_t, const RgState &, const RgMsgs &, bool, const u64 *, const u32 *, u64, u64 *, const RgListOut &);
-extern template void rg_launch_tick_fused_t<6>(hipStream_t, const RgState &, const RgFused &, bool);
-extern template void rg_launch_tick_send_t<6>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIns &, u64, u32, const RgSendCols &, bool);
-extern template void rg_launch_flush_small_t<6>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &);
-extern template void rg_launch_flush_small_send_t<6>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &, const RgSmallSend &);
-extern template void rg_launch_mailbox_t<6>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u32 *, u64 *, u64 *, const RgListOut &, RgMbox *, u64, u64, const RgSmallSend &);
-extern template void rg_launch_tick_t<7>(hipStream_t, const RgState &, const RgMsgs &, u32, bool);
-extern template void rg_launch_tick_classes_t<7>(hipStream_t, const RgState &, const RgMsgs &, int, const RgClasses &);
-extern template void rg_launch_tick_split_t<7>(hipStream_t, const RgState &, const RgMsgs &, u64);
-extern template void rg_launch_tick_list_t<7>(hipStream_t, const RgState &, const RgMsgs &, bool, const u64 *, const u32 *, u64, u64 *, const RgListOut &);
-extern template void rg_launch_tick_fused_t<7>(hipStream_t, const RgState &, const RgFused &, bool);
-extern template void rg_launch_tick_send_t<7>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIns &, u64, u32, const RgSendCols &, bool);
-extern template void rg_launch_flush_small_t<7>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &);
-extern template void rg_launch_flush_small_send_t<7>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &, const RgSmallSend &);
-extern template void rg_launch_mailbox_t<7>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u32 *, u64 *, u64 *, const RgListOut &, RgMbox *, u64, u64, const RgSmallSend &);
-extern template void rg_launch_tick_t<8>(hipStream_t, const RgState &, const RgMsgs &, u32, bool);
-extern template void rg_launch_tick_classes_t<8>(hipStream_t, const RgState &, const RgMsgs &, int, const RgClasses &);
-extern template void rg_launch_tick_split_t<8>(hipStream_t, const RgState &, const RgMsgs &, u64);
-extern template void rg_launch_tick_list_t<8>(hipStream_t, const RgState &, const RgMsgs &, bool, const u64 *, const u32 *, u64, u64 *, const RgListOut &);
-extern template void rg_launch_tick_fused_t<8>(hipStream_t, const RgState &, const RgFused &, bool);
-extern template void rg_launch_tick_send_t<8>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIns &, u64, u32, const RgSendCols &, bool);
-extern template void rg_launch_flush_small_t<8>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &);
-extern template void rg_launch_flush_small_send_t<8>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u64 *, u64 *, const RgListOut &, const RgSmallSend &);
-extern template void rg_launch_mailbox_t<8>(hipStream_t, const RgState &, const RgMsgs &, bool, const RgIngest &, u32 *, u64 *, u64 *, const RgListOut &, RgMbox *, u64, u64, const RgSmallSend &);
 #endif
