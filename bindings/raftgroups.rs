@@ -5,7 +5,7 @@
 use std::os::raw::{c_char, c_void};
 
 pub const RG_MAX_SLOTS: u32 = 8;
-pub const RG_ABI_VERSION: u32 = 7;
+pub const RG_ABI_VERSION: u32 = 8;
 pub const RG_PF_STATE_MASK: u32 = 0x03;
 pub const RG_STATE_PROBE: u32 = 0;
 pub const RG_STATE_REPLICATE: u32 = 1;
@@ -58,6 +58,14 @@ pub const RG_EV_UNREACHABLE: u32 = 1;
 pub const RG_EV_SNAPSHOT_FINISH: u32 = 2;
 pub const RG_EV_SNAPSHOT_FAILURE: u32 = 3;
 pub const RG_MAX_FUSE: u32 = 8;
+pub const RG_READ_MAX_DEPTH: u32 = 16;
+pub const RG_READ_LEASE: u32 = 0x1;
+pub const RG_READ_NOT_READY: u32 = 0;
+pub const RG_READ_READY: u32 = 1;
+pub const RG_READ_QUEUED: u32 = 2;
+pub const RG_READ_DUPLICATE: u32 = 3;
+pub const RG_READ_FULL: u32 = 4;
+pub const RG_READ_ACK_LAST_SELF: u32 = 0x1;
 pub const RG_SEND_APPEND: u32 = 1;
 pub const RG_SEND_SNAPSHOT: u32 = 2;
 pub const RG_SEND_HOST: u32 = 3;
@@ -220,6 +228,27 @@ pub struct RgResolvedHint {
     pub hint: u64,
     pub slot: u32,
     pub reserved: u32,
+}
+
+#[repr(C)]
+pub struct RgReadReq {
+    pub group: u64,
+    pub ctx: u64,
+}
+
+#[repr(C)]
+pub struct RgReadAck {
+    pub group: u64,
+    pub ctx: u64,
+    pub slot: u32,
+    pub flags: u32,
+}
+
+#[repr(C)]
+pub struct RgReadState {
+    pub group: u64,
+    pub ctx: u64,
+    pub index: u64,
 }
 
 #[repr(C)]
@@ -438,6 +467,13 @@ extern "C" {
     pub fn rg_vote_result(h: *mut RgEngine, host_yes: *const u8, host_no: *const u8, host_result: *mut u8) -> i32;
     pub fn rg_tally_votes(h: *mut RgEngine, host_yes: *const u8, host_no: *const u8, host_granted: *mut u8, host_rejected: *mut u8, host_result: *mut u8) -> i32;
     pub fn rg_quorum_recently_active(h: *mut RgEngine, host_result: *mut u8) -> i32;
+    pub fn rg_read_index_enable(h: *mut RgEngine, depth: u32) -> i32;
+    pub fn rg_read_index(h: *mut RgEngine, host_reqs: *const RgReadReq, n: u64, flags: u32, host_status: *mut u8) -> i32;
+    pub fn rg_read_acks(h: *mut RgEngine, host_acks: *const RgReadAck, n: u64) -> i32;
+    pub fn rg_read_acks_device(h: *mut RgEngine, dev_ctx: *const u64) -> i32;
+    pub fn rg_read_states(h: *mut RgEngine, host_items: *mut RgReadState, cap: u64, n: *mut u64) -> i32;
+    pub fn rg_read_last_pending(h: *mut RgEngine, dev_ctx_g: *mut u64, host_ctx_g: *mut u64) -> i32;
+    pub fn rg_read_pending_counts(h: *mut RgEngine, host_counts: *mut u8) -> i32;
     pub fn rg_set_peers(h: *mut RgEngine, group: u64, peer_ids: *const u64, n: u32, term: u64) -> i32;
     pub fn rg_step(h: *mut RgEngine, group: u64, m: *const RgAppendResponse) -> i32;
     pub fn rg_step_heartbeat_response(h: *mut RgEngine, group: u64, from: u64, term: u64, commit: u64, ins_full: u8) -> i32;

@@ -41,7 +41,7 @@ extern "C" {
  * new members keep the old meaning), so a caller is compiled against the header of the library it loads. RG_ABI_VERSION is bumped
  * whenever a struct layout, an enum value or a signature changes; rg_abi_version() returns what the library was built with --
  * compare the two at start-up (raftgroups.hpp and the Python / Rust bindings do). */
-#define RG_ABI_VERSION 7u
+#define RG_ABI_VERSION 8u
 
 /* ---- status codes; the negative values mirror src/errors.rs:6-50 where one applies ----
  * Every entry point that returns int returns one of these and leaves the text in rg_last_error() (per thread). Nothing unwinds
@@ -532,6 +532,76 @@ int rg_tally_votes(rg_engine *h, const uint8_t *host_yes, const uint8_t *host_no
 /* quorum_recently_active for every group: result u8[G] (1 = active quorum); clears recent_active of
  * every other slot and sets the self slot's, exactly as tracker.rs:346-361. */
 int rg_quorum_recently_active(rg_engine *h, uint8_t *host_result);
+
+/* ---- ReadIndex: "may I serve this read?" (MsgReadIndex, src/raft.rs:2056-2091; the read-only half of
+ *      handle_heartbeat_response, src/raft.rs:1805-1818; the queue itself, src/read_only.rs:86-139) ----
+ * The read index of a request is raft_log.committed when it arrives; whether it may be served depends on
+ * commit_to_current_term() (src/raft.rs:581) and on ProgressTracker::has_quorum(acks) (src/tracker.rs:367-372) over the voter
+ * configuration: RG_COL_COMMIT, RG_COL_TERM_LO and RG_COL_CFG, all of which live on the device. So does, once enabled, one
+ * bounded FIFO of pending reads per group (ReadOnly.read_index_queue + pending_read_index): entries {ctx, index, acks}.
+ * The reference keys them by the request's context BYTES; the host keeps that map and hands the engine a 64-bit HANDLE per
+ * context: non-zero and unique among the group's pending reads (0 stands for an empty Message.context).
+ *   Term changes: Raft::reset replaces the ReadOnly (src/raft.rs:957). The engine does it lazily -- every call below first
+ *   compares the group's RG_COL_CUR_TERM with the term its queue last saw and, if they differ, empties the queue without
+ *   emitting anything -- so no tick changes.
+ *   Order: the records of one group in one call are applied in array order; between calls, call order. The read-only half and
+ *   the Progress half of a heartbeat response (RG_MF_HEARTBEAT of a tick) share no state: either may go first.
+ *   Read states (Raft.read_states / the MsgReadIndexResp the host builds, handle_ready_read_index src/raft.rs:2790)
+ *   accumulate in ONE compact device list until rg_read_states drains it. A group's states are contiguous inside what one call
+ *   appended and in queue order; the order between groups is unspecified.
+ * Every call before rg_read_index_enable returns RG_ERR_STATE. Checkpoints (rg_checkpoint / rg_restore) include the queues,
+ * not the undrained list; rg_permute_groups carries the queues (drain the list first: its `group` fields name old positions). */
+#define RG_READ_MAX_DEPTH 16
+/* Allocate the queues: `depth` (1..RG_READ_MAX_DEPTH) pending reads per group, 17 * depth + 12 bytes per group. Once. */
+int rg_read_index_enable(rg_engine *h, uint32_t depth);
+typedef struct {
+    uint64_t group;
+    uint64_t ctx; /* the context's handle, non-zero */
+} rg_read_req;
+#define RG_READ_LEASE 0x1u /* rg_read_index flags: ReadOnlyOption::LeaseBased (src/read_only.rs:30-35) for the whole call; else Safe */
+/* host_status[i] of request i: */
+#define RG_READ_NOT_READY 0u /* commit_to_current_term() is false (commit < RG_COL_TERM_LO): dropped (src/raft.rs:2057-2061) */
+#define RG_READ_READY 1u     /* a singleton group (src/quorum/joint.rs:77) or RG_READ_LEASE: read state {group, ctx, commit} emitted at once */
+#define RG_READ_QUEUED 2u    /* pushed {ctx, index = commit, acks = {self}}: the host broadcasts a heartbeat carrying ctx */
+#define RG_READ_DUPLICATE 3u /* ctx is already pending: nothing queued (src/read_only.rs:89-91); the host STILL broadcasts the
+                                heartbeat with that ctx (src/raft.rs:2077-2081) */
+#define RG_READ_FULL 4u      /* `depth` reads are pending: nothing queued, nothing emitted -- the one bound the reference does
+                                not have; the host retries after acks have drained the queue */
+/* Step n MsgReadIndex requests. host_status (u8 [n], may be NULL) receives RG_READ_* per request. RG_ERR_INVALID_ARG (and nothing
+ * applied) for a group beyond the shard or a zero ctx. Synchronises. */
+int rg_read_index(rg_engine *h, const rg_read_req *host_reqs, uint64_t n, uint32_t flags, uint8_t *host_status);
+/* The read-only half of a MsgHeartbeatResponse from `slot` carrying context `ctx`: recv_ack, and if has_quorum(acks) -- the
+ * voters of both majorities; a learner's ack is recorded and never counts -- advance: every pending read from the oldest
+ * through `ctx` becomes a read state. ctx = 0, a ctx that is not pending and a slot without a Progress (RG_CFG_PRESENT) do
+ * nothing. RG_READ_ACK_LAST_SELF: the re-check after a configuration change (post_conf_change, src/raft.rs:2650-2664: "the
+ * quorum size is now smaller") -- the group's LAST pending read is acked from the leader's own slot; `slot` and `ctx` are
+ * ignored. Call it after rg_set_config. */
+typedef struct {
+    uint64_t group;
+    uint64_t ctx;
+    uint32_t slot;
+    uint32_t flags; /* RG_READ_ACK_* */
+} rg_read_ack;
+#define RG_READ_ACK_LAST_SELF 0x1u
+int rg_read_acks(rg_engine *h, const rg_read_ack *host_acks, uint64_t n); /* synchronises (control path) */
+/* The dense form: one heartbeat round of EVERY group. dev_ctx: u64 [P][stride] in DEVICE memory, the layout of a tick's message
+ * columns -- cell (slot, group) = the context handle of that peer's heartbeat response, 0 = none; slots are applied in
+ * ascending order. A group with nothing pending costs the read of one 4-byte word. Asynchronous. */
+int rg_read_acks_device(rg_engine *h, const uint64_t *dev_ctx);
+typedef struct {
+    uint64_t group;
+    uint64_t ctx;
+    uint64_t index; /* ReadState.index */
+} rg_read_state;
+/* Drain the list: up to `cap` states to host_items, *n = how many there were (it may exceed cap: only cap are written, ALL are
+ * drained -- cap = 0 drains nothing and only reports *n, so a caller can size its array). Synchronises. */
+int rg_read_states(rg_engine *h, rg_read_state *host_items, uint64_t cap, uint64_t *n);
+/* ReadOnly::last_pending_request_ctx (src/read_only.rs:132-134) of every group, 0 = none -> u64 [G] in DEVICE memory
+ * (dev_ctx_g) or, when host_ctx_g is not NULL, copied to the host: what every regular bcast_heartbeat attaches
+ * (src/raft.rs:876). Asynchronous unless a host destination is given. */
+int rg_read_last_pending(rg_engine *h, uint64_t *dev_ctx_g, uint64_t *host_ctx_g);
+/* ReadOnly::pending_read_count (src/read_only.rs:136-139) of every group -> host u8 [G]. Synchronises. */
+int rg_read_pending_counts(rg_engine *h, uint8_t *host_counts);
 
 /* ---- message-at-a-time host mirror of RawNode::step for MsgAppendResponse
  *      (src/raw_node.rs:402-411 -> src/raft.rs:1280-1411 term gate -> :2096-2098) ---- */

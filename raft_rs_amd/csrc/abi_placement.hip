@@ -84,13 +84,14 @@ extern "C" int rg_permute_groups(rg_engine *h, const uint64_t *host_perm) try {
     if (rc) return rc;
     rc = rg_send_materialize(h); // (the compact list keeps the OLD positions in its `group` field: fetch it before this call)
     if (rc) return rc;
-    char *tmp = nullptr, *itmp = nullptr;
+    char *tmp = nullptr, *itmp = nullptr, *rtmp = nullptr;
     u64 *d_perm = nullptr;
     u32 *etmp = nullptr;
     hipError_t e = hipMalloc(&tmp, h->state_bytes);
     if (e == hipSuccess) e = hipMalloc(&d_perm, h->G * 8);
     if (e == hipSuccess && h->ins_arena) e = hipMalloc(&itmp, h->ins_state_bytes);
     if (e == hipSuccess && h->esz) e = hipMalloc(&etmp, (size_t)h->G * h->ins.esz_w * 4);
+    if (e == hipSuccess && h->rd) e = hipMalloc(&rtmp, h->rd->bytes);
     if (e == hipSuccess) e = hipMemcpyAsync(d_perm, host_perm, h->G * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(tmp, h->arena, h->state_bytes, hipMemcpyDeviceToDevice, h->stream); // (padding and all)
     if (e == hipSuccess) {
@@ -129,6 +130,21 @@ extern "C" int rg_permute_groups(rg_engine *h, const uint64_t *host_perm) try {
         if (e == hipSuccess) e = hipMemcpyAsync(h->esz, etmp, (size_t)h->G * words * 4, hipMemcpyDeviceToDevice, h->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess && h->rd) { // ... and the pending-read queues of ReadIndex (ring slots are rows of depth-major columns)
+        RgReadEngine *rd = h->rd;
+        e = hipMemcpyAsync(rtmp, rd->arena, rd->bytes, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) {
+            rg_place_rows<u32>(h, rd->cols.qw, rtmp, d_perm, 1);
+            rg_place_rows<u64>(h, rd->cols.qterm, rtmp + rd->off_qterm, d_perm, 1);
+            rg_place_rows<u64>(h, rd->cols.ctx, rtmp + rd->off_ctx, d_perm, rd->cols.depth);
+            rg_place_rows<u64>(h, rd->cols.idx, rtmp + rd->off_idx, d_perm, rd->cols.depth);
+            rg_place_rows<u8>(h, rd->cols.acks, rtmp + rd->off_acks, d_perm, rd->cols.depth);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(rd->arena, rtmp, rd->bytes, hipMemcpyDeviceToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    }
+    if (rtmp) (void)hipFree(rtmp);
     if (tmp) (void)hipFree(tmp);
     if (itmp) (void)hipFree(itmp);
     if (etmp) (void)hipFree(etmp);
@@ -166,6 +182,10 @@ extern "C" int rg_permute_groups(rg_engine *h, const uint64_t *host_perm) try {
     if (h->esz_ckpt) {
         (void)hipFree(h->esz_ckpt);
         h->esz_ckpt = nullptr;
+    }
+    if (h->rd && h->rd->ckpt) {
+        (void)hipFree(h->rd->ckpt);
+        h->rd->ckpt = nullptr;
     }
     return RG_OK;
 } RG_ABI_GUARD

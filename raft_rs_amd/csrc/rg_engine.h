@@ -25,6 +25,7 @@
 #include "rg_send.h"
 #include "rg_wire.h"
 #include "rg_workload.h"
+#include "rg_read.h"
 
 #include "rg_tick_kernels.h"
 
@@ -92,6 +93,24 @@ RG_HD u32 rg_cfg_slots_named(u32 cfg) {
 // the smallest body k_tick_classes<P> has for k slots (3, 5, 7 below P; P)
 RG_HD u32 rg_class_body(u32 k, u32 P) { return (P > 3 && k <= 3) ? 3u : (P > 5 && k <= 5) ? 5u : (P > 7 && k <= 7) ? 7u : P; }
 
+// ReadIndex (abi_read.hip; rg_permute_groups gathers the columns): the optional arena -- absent until rg_read_index_enable, like
+// the entry-size windows of rg_log_sizes_enable -- and the list of read states.
+struct RgReadEngine {
+    RgReadCols cols;
+    char *arena, *ckpt; // qw | qterm | ctx | idx | acks; the checkpoint copy (lazy)
+    size_t bytes;
+    size_t off_qterm, off_ctx, off_idx, off_acks;
+    rg_read_state *items;      // the compact list of read states
+    u64 cap;                   // ... its capacity, items
+    unsigned long long *count; // device: states in the list
+    // An upper bound of (states in the list + reads pending in the queues): every state answers exactly one request that was
+    // accepted (READY or QUEUED), so the list cannot outgrow it -- the capacity is raised on the control path, before a request
+    // call, and no kernel ever has to drop or to size per group for the worst case.
+    u64 outstanding, ckpt_outstanding;
+    std::vector<char> stage;   // host staging of one batch: RgReadRec[n] | u32 run_start[runs + 1] | u8 status[n]
+    std::vector<RgReadRec> recs;
+};
+
 // ------------------------------------------------------------------------------------------------
 // engine object
 // ------------------------------------------------------------------------------------------------
@@ -142,7 +161,8 @@ struct rg_engine {
     char *ins_arena;   // meta | head | tail | ring | items | counter
     char *ins_ckpt;    // checkpoint copy of meta | ring (lazy)
     u32 *esz, *esz_ckpt; // entry sizes for RG_SEND_BYTES (rg_log_sizes_enable), u32 [G][esz_w]; checkpoint copy (lazy)
-    void *d_recs;      // staging for rg_log_sizes_write / rg_update_state records
+    struct RgReadEngine *rd; // ReadIndex: pending-read queues and the list of read states (rg_read_index_enable), nullptr = off
+    void *d_recs;      // staging for rg_log_sizes_write / rg_update_state / rg_read_index records
     size_t d_recs_cap;
     // resident small-batch path (rg_mailbox_start): request / answer block in pinned host memory, whether the feature is
     // on, whether the host has launched an instance it has not seen leave, the last request number
@@ -282,4 +302,8 @@ int rg_fix_ins_full(rg_engine *h); // k_fix_ins_full over every group, on the en
 int rg_ensure_sparse(rg_engine *h);
 // abi_publish.hip
 int rg_rccl_load();
+// abi_read.hip: the optional ReadIndex arena in the calls that handle every arena (all of them no-ops while it is absent)
+void rg_read_free(rg_engine *h);
+int rg_read_checkpoint(rg_engine *h);
+int rg_read_restore(rg_engine *h);
 

@@ -206,7 +206,7 @@ class PublishStats(C.Structure):
                 ("events_on_tick_packets", C.c_uint64)]
 
 
-ABI_VERSION = 7  # RG_ABI_VERSION of include/raftgroups.h these ctypes layouts mirror (tests/test_abi.py compares)
+ABI_VERSION = 8  # RG_ABI_VERSION of include/raftgroups.h these ctypes layouts mirror (tests/test_abi.py compares)
 class CommInfo(C.Structure):
     _fields_ = [("rank", C.c_uint32), ("world", C.c_uint32), ("transport", C.c_uint32), ("in_process", C.c_uint32),
                 ("rccl_ranks", C.c_uint32), ("rccl_rank", C.c_uint32)]
@@ -227,6 +227,14 @@ EV_UNREACHABLE, EV_SNAPSHOT_FINISH, EV_SNAPSHOT_FAILURE = 1, 2, 3
 SEND_ITEM_DTYPE = np.dtype([("group", "<u8"), ("prev_index", "<u8"), ("last_index", "<u8"), ("slot", "<u4"),
                             ("n_msgs", "<u2"), ("kind", "<u2")])
 assert SEND_ITEM_DTYPE.itemsize == 32
+# ReadIndex (rg_read_index_enable ...)
+READ_REQ_DTYPE = np.dtype([("group", "<u8"), ("ctx", "<u8")])                                     # rg_read_req
+READ_ACK_DTYPE = np.dtype([("group", "<u8"), ("ctx", "<u8"), ("slot", "<u4"), ("flags", "<u4")])  # rg_read_ack
+READ_STATE_DTYPE = np.dtype([("group", "<u8"), ("ctx", "<u8"), ("index", "<u8")])                 # rg_read_state
+READ_LEASE = 1
+READ_ACK_LAST_SELF = 1
+READ_NOT_READY, READ_READY, READ_QUEUED, READ_DUPLICATE, READ_FULL = 0, 1, 2, 3, 4
+READ_MAX_DEPTH = 16
 
 # every symbol include/raftgroups.h declares: (restype, argtypes)
 _vp, _u64, _i = C.c_void_p, C.c_uint64, C.c_int
@@ -293,6 +301,13 @@ SYMBOLS = {
     "rg_vote_result": (_i, [_vp, _vp, _vp, _vp]),
     "rg_tally_votes": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "rg_quorum_recently_active": (_i, [_vp, _vp]),
+    "rg_read_index_enable": (_i, [_vp, C.c_uint32]),
+    "rg_read_index": (_i, [_vp, _vp, _u64, C.c_uint32, _vp]),
+    "rg_read_acks": (_i, [_vp, _vp, _u64]),
+    "rg_read_acks_device": (_i, [_vp, _vp]),
+    "rg_read_states": (_i, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    "rg_read_last_pending": (_i, [_vp, _vp, _vp]),
+    "rg_read_pending_counts": (_i, [_vp, _vp]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -818,6 +833,51 @@ class Engine:
         res = np.empty(self.n_groups, dtype=np.uint8)
         self._check(self.L.rg_quorum_recently_active(self.h, res.ctypes.data))
         return res
+
+    # ---- ReadIndex: pending-read queues and the ack quorum on the device ---------------------------
+    def read_index_enable(self, depth):
+        """rg_read_index_enable: one FIFO of `depth` (1..16) pending reads per group."""
+        self._check(self.L.rg_read_index_enable(self.h, depth))
+
+    def read_index(self, reqs, lease=False):
+        """Step MsgReadIndex requests: reqs is a READ_REQ_DTYPE array (or [(group, ctx)]) -> u8[n] of READ_* statuses."""
+        reqs = np.ascontiguousarray(np.array(reqs, dtype=READ_REQ_DTYPE))
+        status = np.zeros(len(reqs), dtype=np.uint8)
+        self._check(self.L.rg_read_index(self.h, reqs.ctypes.data, len(reqs), READ_LEASE if lease else 0, status.ctypes.data))
+        return status
+
+    def read_acks(self, acks):
+        """The read-only halves of heartbeat responses: a READ_ACK_DTYPE array (or [(group, ctx, slot, flags)])."""
+        acks = np.ascontiguousarray(np.array(acks, dtype=READ_ACK_DTYPE))
+        self._check(self.L.rg_read_acks(self.h, acks.ctypes.data, len(acks)))
+
+    def read_acks_device(self, dev_ctx):
+        """One heartbeat round of every group: dev_ctx = device pointer to u64 [P][stride] context handles (asynchronous)."""
+        self._check(self.L.rg_read_acks_device(self.h, _ptr(dev_ctx)))
+
+    def read_states(self, cap=None):
+        """Drain the list of read states -> READ_STATE_DTYPE array. With `cap`: (the first cap states, how many there were)."""
+        n = _u64(0)
+        if cap is not None:
+            items = np.zeros(cap, dtype=READ_STATE_DTYPE)
+            self._check(self.L.rg_read_states(self.h, items.ctypes.data, cap, C.byref(n)))
+            return items[:min(cap, n.value)], n.value
+        self._check(self.L.rg_read_states(self.h, None, 0, C.byref(n)))  # (cap = 0 only counts)
+        items = np.zeros(max(n.value, 1), dtype=READ_STATE_DTYPE)
+        self._check(self.L.rg_read_states(self.h, items.ctypes.data, len(items), C.byref(n)))
+        return items[:n.value]
+
+    def read_last_pending(self):
+        """last_pending_request_ctx per group (0 = none): what a regular bcast_heartbeat attaches -> u64[G] (host copy)."""
+        ctx = np.empty(self.n_groups, dtype=np.uint64)
+        self._check(self.L.rg_read_last_pending(self.h, None, ctx.ctypes.data))
+        return ctx
+
+    def read_pending_counts(self):
+        """pending_read_count per group -> u8[G]."""
+        counts = np.empty(self.n_groups, dtype=np.uint8)
+        self._check(self.L.rg_read_pending_counts(self.h, counts.ctypes.data))
+        return counts
 
     # ---- message-at-a-time mirror of RawNode::step -----------------------------------------------
     def set_peers(self, group, peer_ids, term):
