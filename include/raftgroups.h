@@ -586,7 +586,8 @@ typedef struct {
 int rg_read_acks(rg_engine *h, const rg_read_ack *host_acks, uint64_t n); /* synchronises (control path) */
 /* The dense form: one heartbeat round of EVERY group. dev_ctx: u64 [P][stride] in DEVICE memory, the layout of a tick's message
  * columns -- cell (slot, group) = the context handle of that peer's heartbeat response, 0 = none; slots are applied in
- * ascending order. A group with nothing pending costs the read of one 4-byte word. Asynchronous. */
+ * ascending order. A group with nothing pending costs the read of one 4-byte word. Asynchronous.
+ * Not for capture into a hipGraph: the list's pointer and capacity are kernel arguments, and a later growth frees that list. */
 int rg_read_acks_device(rg_engine *h, const uint64_t *dev_ctx);
 typedef struct {
     uint64_t group;

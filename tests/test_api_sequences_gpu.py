@@ -28,16 +28,22 @@ def records(msgs, groups, P, rng):
     return arr
 
 
-def mirror_steps(rg, eng, msgs, groups, P, self_slot):
-    """Feed one tick's events of `groups` through the message-at-a-time mirror."""
+def mirror_steps(rg, eng, msgs, groups, P, self_slot, term=TERM):
+    """Feed one tick's events of `groups` through the message-at-a-time mirror. term: Message.term of the responses (0: a
+    local message, the mirror's term gate is skipped). RG_MF_BECOME_LEADER on the leader's slot -- alone there: the election
+    goes in before anything else of its group -- is rg_local_become_leader at the term in m_hint."""
     MF = rg.MF
     for g in groups:
         g = int(g)
+        if int(msgs["m_flags"][g, self_slot[g]]) == MF.BECOME_LEADER:
+            eng.local_become_leader(g, int(msgs["m_hint"][self_slot[g], g]))
         for p in range(P):
             f = int(msgs["m_flags"][g, p])
             if not f:
                 continue
             if p == self_slot[g]:
+                if f == MF.BECOME_LEADER:
+                    continue
                 if f & MF.APPEND:
                     eng.local_append(g, int(msgs["m_commit"][p, g]))
                 if f & MF.VALID:
@@ -46,9 +52,9 @@ def mirror_steps(rg, eng, msgs, groups, P, self_slot):
             if f & MF.SENT:
                 eng.mark_sent(g, p + 1)
             if f & MF.HEARTBEAT:
-                eng.step_heartbeat_response(g, p + 1, TERM, int(msgs["m_commit"][p, g]), bool(f & MF.INS_FULL))
+                eng.step_heartbeat_response(g, p + 1, term, int(msgs["m_commit"][p, g]), bool(f & MF.INS_FULL))
             elif f & MF.VALID:
-                eng.step(g, p + 1, TERM, int(msgs["m_index"][p, g]), commit=int(msgs["m_commit"][p, g]),
+                eng.step(g, p + 1, term, int(msgs["m_index"][p, g]), commit=int(msgs["m_commit"][p, g]),
                          reject=bool(f & MF.REJECT), reject_hint=int(msgs["m_hint"][p, g]),
                          request_snapshot=int(msgs["m_rs"][p, g]) if f & MF.HAS_RS else 0, ins_full=bool(f & MF.INS_FULL))
 
@@ -473,4 +479,219 @@ def test_random_api_sequences_with_publication(rg, seed, P):
     assert window is None
     assert windows_closed >= 2 and exact_checks >= 5, (windows_closed, exact_checks)
     assert {"fused_lt", "permute", "load_commit", "restore", "mirror_dense", "recompute"} <= ops_seen, ops_seen
+    eng.close()
+
+
+@pytest.mark.parametrize("seed,P", [(31, 3), (34, 5)])
+def test_random_api_sequences_with_read_index(rg, seed, P):
+    """ReadIndex behind every road that moves what it reads (RG_COL_COMMIT, RG_COL_TERM_LO, RG_COL_CUR_TERM, RG_COL_CFG): dense
+    ticks from host and device buffers, fused calls with and without log-term ticks, sparse ticks, mirror flushes -- large,
+    and small ones the resident mailbox workgroup serves --, rg_recompute, rg_set_config followed by the re-check,
+    checkpoint / restore, rg_load_column(COMMIT) and rg_permute_groups, elections on every road that ticks. After EVERY call:
+    a batch of read requests, then sparse or dense acks, straight behind the call on the engine's stream and before anything
+    is read back; statuses, queues and (every few steps) the drained list against tests/readonly_model.py, whose commit,
+    term_lo, term and cfg are the ORACLE's after that call -- never the engine's columns --, and then the state itself
+    against the oracle."""
+    import copy
+    import torch
+    import readonly_model as M
+    from test_read_index_gpu import ReadChecker
+    COL, MF = rg.COL, rg.MF
+    rng = np.random.default_rng(4600 + seed)
+    G, DEPTH, STEPS = 600, 2, 60
+    st = O.add_term_table(O.alloc_state(G, P))
+    st["cfg"][:] = fuzz.random_cfg(rng, G, P)
+    fuzz.random_state(rng, st, small_values=True)
+    fuzz.random_term_table(rng, st, TERM, max_runs=2)  # (room for the elections: no reject is handed back to the host)
+    self_slot = ((st["cfg"] >> 16) & 7).astype(np.int64)
+    eng = rg.Engine(G, P)
+    eng.load_state(st)
+    for g in range(G):
+        eng.set_peers(g, list(range(1, P + 1)), TERM)
+    eng.mailbox_start()
+    eng.read_index_enable(DEPTH)
+    cl = O.Cluster(G)
+    cl.load_soa(st, term=TERM)
+    msgs = O.alloc_msgs(G, P)
+    del msgs["m_logterm"]
+    mb = rg.MsgBuffers(G, P, eng.stride)
+    gout = np.zeros(G, dtype=np.uint32)
+    out_t = torch.zeros((8, G), dtype=torch.int32, device="cuda")
+    rd = ReadChecker(eng, M.Shard(st["cfg"], DEPTH), rng, P, DEPTH, G)
+    ckpt = None
+    ops_seen, seen, drained, elected = set(), set(), 0, 0
+    served_before_read = []  # steps whose flush the resident workgroup served (the read calls follow it at once)
+
+    def reload_oracle():
+        nonlocal cl
+        cl = O.Cluster(G)
+        cl.load_soa(st, term=TERM)
+
+    def model_follows_the_oracle():
+        for g, grp in enumerate(rd.model.groups):
+            grp.cfg, grp.commit, grp.term_lo = int(st["cfg"][g]), int(st["commit"][g]), int(st["term_lo"][g])
+            grp.set_term(int(st["cur_term"][g]))
+
+    def reads(step):
+        nonlocal seen
+        seen |= set(rd.requests(rd.random_requests(150), lease=(step % 10 == 9)))
+        if step % 3 != 2:
+            rd.acks(rd.random_sparse_acks(250))
+        else:
+            rd.acks_dense(rd.random_dense_cols(0.5))
+        rd.check_queues()
+
+    def check_state(step, op, check_out):
+        got = eng.read_state()
+        cl.store_soa(st)
+        diffs = fuzz.diff_states(st, got, G, P)
+        assert not diffs, (step, op, diffs[:5])
+        assert (eng.read_column(COL.CUR_TERM) == st["cur_term"]).all(), (step, op)
+        if check_out:
+            assert (got["out"] == gout).all(), (step, op, np.nonzero(got["out"] != gout)[0][:5])
+
+    def one_tick(step, op, sub=0):
+        """one tick of random messages through the road `op`; the oracle takes the same messages"""
+        nonlocal elected
+        term = TERM + 1 + 2 * step + sub  # (above every term a group can have: the elections are well-formed)
+        fuzz.random_msgs(rng, st, msgs, elect_p=0.0 if op.startswith("mirror") else 0.04, elect_term=term)
+        touched = None
+        if op in ("sparse3", "sparse1", "mirror_sparse", "mirror_small"):
+            hi = 30 if op == "mirror_small" else G // 3  # (mirror_small: <= 256 records, what the resident workgroup takes)
+            touched = np.sort(rng.choice(G, size=int(rng.integers(1, hi)), replace=False))
+            keep = np.zeros(G, dtype=bool)
+            keep[touched] = True
+            msgs["m_flags"][~keep] = 0
+        if op.startswith("mirror"):
+            clean_for_mirror(msgs, P, self_slot)
+            for g in (touched if touched is not None else range(G)):
+                if rng.random() < 0.08:  # rg_local_become_leader: the election alone on the leader's slot
+                    msgs["m_flags"][g, self_slot[g]] = MF.BECOME_LEADER
+                    msgs["m_hint"][self_slot[g], g] = term
+        keep_alive = None
+        if op == "dense":
+            for k in ("m_index", "m_commit", "m_hint", "m_rs", "m_flags"):
+                getattr(mb, k)[...] = msgs[k]
+            eng.tick(mb)
+        elif op == "device":
+            keep_alive = _to_device(torch, msgs, False)
+            torch.cuda.synchronize()
+            eng.tick_device(*[c.data_ptr() for c in keep_alive])
+        elif op == "sparse3":
+            assert eng.ingest(records(msgs, touched, P, rng)) == 0
+            eng.tick_ingested()
+        elif op == "sparse1":
+            assert eng.ingest_tick(records(msgs, touched, P, rng))[1] == 0
+        else:
+            mirror_steps(rg, eng, msgs, touched if touched is not None else range(G), P, self_slot, term=0)
+            served = eng.mailbox_stats()[0]
+            eng.flush()
+            if eng.mailbox_stats()[0] > served:
+                served_before_read.append(step)
+        gout[:] = 0
+        cl.tick_soa(msgs, gout)
+        cl.store_soa(st)
+        elected += int(((gout & 0x10) != 0).sum())
+        return keep_alive
+
+    for step in range(STEPS):
+        cl.store_soa(st)
+        op = rng.choice(["dense", "device", "fused", "fused_lt", "sparse3", "sparse1", "mirror_sparse", "mirror_small", "mirror_dense",
+                         "recompute", "set_config", "checkpoint", "restore", "load_commit", "permute"],
+                        p=[0.08, 0.08, 0.07, 0.07, 0.08, 0.08, 0.07, 0.12, 0.05, 0.05, 0.06, 0.05, 0.05, 0.05, 0.04])
+        if op == "restore" and ckpt is None:
+            op = "checkpoint"
+        ops_seen.add(op)
+        check_out, keep_alive = True, None
+        if op == "checkpoint":
+            eng.checkpoint()
+            ckpt = ({k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in st.items()}, self_slot.copy(),
+                    copy.deepcopy(rd.model.groups))
+            check_out = False
+        elif op == "restore":
+            eng.restore()
+            st = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in ckpt[0].items()}
+            self_slot = ckpt[1].copy()
+            rd.model.groups = copy.deepcopy(ckpt[2])  # (the queues of the checkpoint; the undrained list stays)
+            reload_oracle()
+            check_out = False
+        elif op == "load_commit":
+            c = st["commit"].copy()
+            up = rng.choice(G, size=40, replace=False)
+            c[up] = np.maximum(c[up], np.minimum(st["term_hi"][up], c[up] + 3))
+            eng.load_column(COL.COMMIT, c)
+            st["commit"][:] = c
+            reload_oracle()
+            check_out = False
+        elif op == "permute":
+            drained += rd.check_states()  # (the list's `group` fields name the old positions: drain first)
+            perm = rng.permutation(G).astype(np.uint64)
+            eng.permute_groups(perm)
+            p = perm.astype(np.int64)
+            for k in ("match", "next", "pr_commit", "pend_snap", "pend_rs", "gid", "run_first", "run_term"):
+                st[k][:, :G] = st[k][:, p]
+            for k in ("pflags", "commit", "term_lo", "term_hi", "cfg", "dummy_index", "dummy_term", "cur_term"):
+                st[k][:] = st[k][p]
+            self_slot = self_slot[p]
+            rd.model.groups = [rd.model.groups[int(i)] for i in p]
+            ckpt = None  # (rg_permute_groups drops the checkpoint: it images the old placement)
+            reload_oracle()
+            check_out = False
+        elif op == "set_config":
+            changed = [int(g) for g in rng.choice(G, size=8, replace=False)]
+            for g in changed:
+                w = int(fuzz.random_cfg(rng, 1, P)[0])
+                if rng.random() < 0.5:  # the quorum shrinks to the leader alone: what the re-check is for
+                    s = int(self_slot[g])
+                    w = (1 << s) | (s << 16) | (int(st["cfg"][g]) & 0xff000000) | (1 << (24 + s))
+                eng.set_config(g, w)
+                st["cfg"][g] = w
+                self_slot[g] = (w >> 16) & 7
+            reload_oracle()
+            model_follows_the_oracle()
+            rd.acks([(g, 0, 0, M.ACK_LAST_SELF) for g in changed])  # post_conf_change
+            check_out = False
+        elif op == "recompute":
+            eng.recompute()
+            for g in range(G):
+                gout[g] = 1 if cl.maybe_commit(g) else 0
+            cl.store_soa(st)
+        elif op in ("fused", "fused_lt"):
+            T = int(rng.integers(1, 5))
+            kinds = ["plain"] * T
+            if op == "fused_lt":
+                kinds[int(rng.integers(0, T))] = "lt"
+            keep_alive = []
+            for t in range(T):
+                fuzz.random_msgs(rng, st, msgs, elect_p=0.02, elect_term=TERM + 1 + 2 * step)
+                if t:  # (one election per group and call: the term of a second one would not be above the first's)
+                    for s in range(P):
+                        msgs["m_flags"][:, s] &= np.where(self_slot == s, 0xff & ~MF.BECOME_LEADER, 0xff).astype(np.uint8)
+                gout[:] = 0
+                cl.tick_soa(msgs, gout)
+                cl.store_soa(st)
+                elected += int(((gout & 0x10) != 0).sum())
+                keep_alive.append(_to_device(torch, msgs, kinds[t] == "lt"))
+            torch.cuda.synchronize()
+            assert eng.tick_device_fused([[c.data_ptr() for c in d] for d in keep_alive], out_t.data_ptr()) == T
+        elif op == "mirror_small":
+            one_tick(step, op)  # (the first makes the engine's last tick a sparse one; the second is the mailbox's to serve)
+            model_follows_the_oracle()
+            reads(step)
+            check_state(step, op, True)
+            one_tick(step, op, sub=1)
+        else:
+            keep_alive = one_tick(step, op)
+        model_follows_the_oracle()
+        reads(step)
+        check_state(step, op, check_out)
+        del keep_alive
+        if step % 4 == 3 or step == STEPS - 1:
+            drained += rd.check_states()
+    assert ops_seen == {"dense", "device", "fused", "fused_lt", "sparse3", "sparse1", "mirror_sparse", "mirror_small", "mirror_dense",
+                        "recompute", "set_config", "checkpoint", "restore", "load_commit", "permute"}, ops_seen
+    assert seen == {M.NOT_READY, M.READY, M.QUEUED, M.DUPLICATE, M.FULL}, seen
+    assert drained > 300 and elected > 20, (drained, elected)
+    served, launches = eng.mailbox_stats()
+    assert len(served_before_read) >= 2 and served >= 2 and launches >= 2, (served_before_read, served, launches)
     eng.close()

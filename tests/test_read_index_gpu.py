@@ -18,9 +18,13 @@ def cfg_make(incoming, outgoing, self_slot, present):
 
 
 def mixed_cfgs(rng, n, P):
-    """majority, joint, learner-carrying and singleton groups, interleaved"""
+    """majority, joint, learner-carrying and singleton groups, interleaved (P = 1: singletons, there is nothing else; P = 2: the
+    learner-carrying kind is one voter and one learner, a singleton as well)"""
     full = (1 << P) - 1
     out = np.zeros(n, dtype=np.uint32)
+    if P == 1:
+        out[:] = cfg_make(1, 0, 0, 1)
+        return out
     for g in range(n):
         k = g % 4
         if k == 0:  # majority over every slot
@@ -40,15 +44,95 @@ def mixed_cfgs(rng, n, P):
     return out
 
 
-class Rig:
+class ReadChecker:
+    """The read calls of an engine and the model's side by side. Whoever drives the engine keeps the model's groups current
+    (cfg / commit / term_lo / set_term) with the state under the queues."""
+
+    def __init__(self, eng, model, rng, P, depth, n):
+        self.eng, self.model, self.rng, self.P, self.depth, self.n = eng, model, rng, P, depth, n
+        self.next_ctx = 1
+
+    # ---- the calls under test, engine and model side by side ----
+    def fresh_ctx(self):
+        self.next_ctx += 1
+        return self.next_ctx - 1 + (1 << 40)  # (handles are 64-bit: keep some high bits in play)
+
+    def requests(self, reqs, lease=False):
+        got = self.eng.read_index(reqs, lease=lease)
+        want = self.model.read_index(reqs, lease)
+        assert [int(x) for x in got] == want, [(r, int(a), b) for r, a, b in zip(reqs, got, want) if int(a) != b][:5]
+        return want
+
+    def acks(self, acks):
+        """acks: [(group, slot, ctx, flags)]"""
+        self.eng.read_acks([(g, ctx, slot, flags) for g, slot, ctx, flags in acks])
+        self.model.read_acks(acks)
+
+    def acks_dense(self, cols):
+        import torch
+        d = torch.from_numpy(cols.view(np.int64).copy()).cuda()
+        torch.cuda.synchronize()
+        self.eng.read_acks_device(d.data_ptr())
+        self.eng.sync()
+        self.model.read_acks_dense(cols)
+
+    def check_queues(self):
+        assert [int(x) for x in self.eng.read_last_pending()] == self.model.last_pending()
+        assert [int(x) for x in self.eng.read_pending_counts()] == self.model.counts()
+
+    def check_states(self):
+        got = self.eng.read_states()
+        assert M.by_group(got.tolist()) == M.by_group(self.model.drain())
+        return len(got)
+
+    # ---- random traffic ----
+    def random_requests(self, n):
+        reqs = []
+        while len(reqs) < n:
+            g = int(self.rng.integers(0, self.n))
+            if self.rng.random() < 0.25:  # several records of one group in one batch: [ctx a, ctx a, ctx b]
+                a, b = self.fresh_ctx(), self.fresh_ctx()
+                reqs += [(g, a), (g, a), (g, b)]
+            else:
+                pend = [c for c, _, _ in self.model.groups[g].queue()]
+                reqs.append((g, int(self.rng.choice(pend)) if pend and self.rng.random() < 0.2 else self.fresh_ctx()))
+        return reqs
+
+    def random_ack_ctx(self, g):
+        pend = [c for c, _, _ in self.model.groups[g].queue()]
+        r = self.rng.random()
+        if pend and r < 0.6:
+            return pend[-1]  # what a follower answers: the last pending ctx its heartbeat carried
+        if pend and r < 0.8:
+            return int(self.rng.choice(pend))
+        return 0 if r < 0.9 else self.fresh_ctx()  # no context / one that is not pending
+
+    def random_sparse_acks(self, n, slot_hi=None):
+        """slots 0 .. slot_hi (default P: not a slot of the engine; up to 8: not a slot of any engine)"""
+        out = []
+        for _ in range(n):
+            g = int(self.rng.integers(0, self.n))
+            out.append((g, int(self.rng.integers(0, (self.P if slot_hi is None else slot_hi) + 1)), self.random_ack_ctx(g), 0))
+        return out
+
+    def random_dense_cols(self, fill):
+        cols = np.zeros((self.P, self.eng.stride), dtype=np.uint64)
+        for g in range(self.n):
+            for s in range(self.P):
+                if self.rng.random() < fill:
+                    cols[s, g] = self.random_ack_ctx(g)
+        return cols
+
+
+class Rig(ReadChecker):
     """An engine with clean leaders (every Progress caught up, Replicate) and the model next to it."""
 
-    def __init__(self, rg, P, depth, seed, n=G, enable=True):
+    def __init__(self, rg, P, depth, seed, n=G, enable=True, cfgs=None):
         self.rg, self.P, self.depth, self.n = rg, P, depth, n
         self.rng = np.random.default_rng(seed)
         self.eng = eng = rg.Engine(n, P)
         stride = eng.stride
-        self.cfg = mixed_cfgs(self.rng, n, P)
+        self.cfg = mixed_cfgs(self.rng, n, P) if cfgs is None else np.array(cfgs, dtype=np.uint32)
         last = self.rng.integers(5, 50, size=n).astype(np.uint64)
         cols = np.zeros((P, stride), dtype=np.uint64)
         cols[:, :n] = last
@@ -139,96 +223,24 @@ class Rig:
         if recheck:  # post_conf_change
             self.acks([(g, 0, 0, M.ACK_LAST_SELF)])
 
-    # ---- the calls under test, engine and model side by side ----
-    def fresh_ctx(self):
-        self.next_ctx += 1
-        return self.next_ctx - 1 + (1 << 40)  # (handles are 64-bit: keep some high bits in play)
 
-    def requests(self, reqs, lease=False):
-        got = self.eng.read_index(reqs, lease=lease)
-        want = self.model.read_index(reqs, lease)
-        assert [int(x) for x in got] == want, [(r, int(a), b) for r, a, b in zip(reqs, got, want) if int(a) != b][:5]
-        return want
-
-    def acks(self, acks):
-        """acks: [(group, slot, ctx, flags)]"""
-        self.eng.read_acks([(g, ctx, slot, flags) for g, slot, ctx, flags in acks])
-        self.model.read_acks(acks)
-
-    def acks_dense(self, cols):
-        import torch
-        d = torch.from_numpy(cols.view(np.int64).copy()).cuda()
-        torch.cuda.synchronize()
-        self.eng.read_acks_device(d.data_ptr())
-        self.eng.sync()
-        self.model.read_acks_dense(cols)
-
-    def check_queues(self):
-        assert [int(x) for x in self.eng.read_last_pending()] == self.model.last_pending()
-        assert [int(x) for x in self.eng.read_pending_counts()] == self.model.counts()
-
-    def check_states(self):
-        got = self.eng.read_states()
-        assert M.by_group(got.tolist()) == M.by_group(self.model.drain())
-        return len(got)
-
-    # ---- random traffic ----
-    def random_requests(self, n):
-        reqs = []
-        while len(reqs) < n:
-            g = int(self.rng.integers(0, self.n))
-            if self.rng.random() < 0.25:  # several records of one group in one batch: [ctx a, ctx a, ctx b]
-                a, b = self.fresh_ctx(), self.fresh_ctx()
-                reqs += [(g, a), (g, a), (g, b)]
-            else:
-                pend = [c for c, _, _ in self.model.groups[g].queue()]
-                reqs.append((g, int(self.rng.choice(pend)) if pend and self.rng.random() < 0.2 else self.fresh_ctx()))
-        return reqs
-
-    def random_ack_ctx(self, g):
-        pend = [c for c, _, _ in self.model.groups[g].queue()]
-        r = self.rng.random()
-        if pend and r < 0.6:
-            return pend[-1]  # what a follower answers: the last pending ctx its heartbeat carried
-        if pend and r < 0.8:
-            return int(self.rng.choice(pend))
-        return 0 if r < 0.9 else self.fresh_ctx()  # no context / one that is not pending
-
-    def random_sparse_acks(self, n):
-        out = []
-        for _ in range(n):
-            g = int(self.rng.integers(0, self.n))
-            out.append((g, int(self.rng.integers(0, self.P + 1)), self.random_ack_ctx(g), 0))  # (slot P: not a slot of the engine)
-        return out
-
-    def random_dense_cols(self, fill):
-        cols = np.zeros((self.P, self.eng.stride), dtype=np.uint64)
-        for g in range(self.n):
-            for s in range(self.P):
-                if self.rng.random() < fill:
-                    cols[s, g] = self.random_ack_ctx(g)
-        return cols
-
-
-@pytest.mark.parametrize("P", [3, 5, 7])
-def test_random_sequences(rg, P):
-    """40 rounds of request batches, sparse and dense acks, ticks that move commit, rg_set_config + re-check and elections, at
-    depth 2 (FULL and ring wrap-around both occur)."""
-    r = Rig(rg, P, depth=2, seed=100 + P)
-    rng = r.rng
+def random_rounds(r, rounds, slot_hi=None):
+    """Rounds of request batches, sparse and dense acks, ticks that move commit, rg_set_config + re-check and elections, every
+    call checked against the model -> (statuses seen, states drained, queues found at their depth after a round)."""
+    rng, P, n = r.rng, r.P, r.n
     seen, drained, at_depth = set(), 0, 0
-    for rnd in range(40):
+    for rnd in range(rounds):
         seen |= set(r.requests(r.random_requests(120), lease=(rnd % 10 == 9)))
         r.check_queues()
         if rnd % 3 != 2:
-            r.acks(r.random_sparse_acks(200))
+            r.acks(r.random_sparse_acks(200, slot_hi))
         else:
             r.acks_dense(r.random_dense_cols(0.5))
         r.check_queues()
         if rnd % 2 == 0:
-            r.tick_advance([int(g) for g in rng.choice(G, size=60, replace=False)])
+            r.tick_advance([int(g) for g in rng.choice(n, size=60, replace=False)])
         if rnd % 4 == 1:
-            for g in rng.choice(G, size=6, replace=False):
+            for g in rng.choice(n, size=6, replace=False):
                 g = int(g)
                 full = (1 << P) - 1
                 c = int(r.cfg[g])
@@ -236,13 +248,24 @@ def test_random_sequences(rg, P):
                 # the quorum shrinks (leave joint, drop voters down to the leader) or the membership is redrawn
                 word = cfg_make(1 << s, 0, s, (c >> 24) & 0xff) if rng.random() < 0.5 else \
                     cfg_make(int(rng.integers(0, full + 1)) | (1 << s), int(rng.integers(0, full + 1)) if rng.random() < 0.4 else 0, s, full)
+                if P == 1:
+                    word &= ~0xff00  # (one slot: every group stays a singleton, never a joint configuration of that one voter)
                 r.set_config(g, word)
         if rnd % 5 == 3:
-            r.tick_elect([int(g) for g in rng.choice(G, size=25, replace=False)])
+            r.tick_elect([int(g) for g in rng.choice(n, size=25, replace=False)])
         r.check_queues()
-        at_depth += sum(1 for grp in r.model.groups if grp.read_only.pending_read_count() == 2)
-        if rnd % 4 == 3 or rnd == 39:
+        at_depth += sum(1 for grp in r.model.groups if grp.read_only.pending_read_count() == r.depth)
+        if rnd % 4 == 3 or rnd == rounds - 1:
             drained += r.check_states()
+    return seen, drained, at_depth
+
+
+@pytest.mark.parametrize("P", [3, 5, 7])
+def test_random_sequences(rg, P):
+    """40 rounds of request batches, sparse and dense acks, ticks that move commit, rg_set_config + re-check and elections, at
+    depth 2 (FULL and ring wrap-around both occur)."""
+    r = Rig(rg, P, depth=2, seed=100 + P)
+    seen, drained, at_depth = random_rounds(r, 40)
     assert seen == {M.NOT_READY, M.READY, M.QUEUED, M.DUPLICATE, M.FULL}
     assert drained > 1000 and at_depth > 100  # (queues that stay full while their head moves: the ring wraps)
     r.close()

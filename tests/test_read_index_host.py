@@ -225,6 +225,7 @@ def make_script(seed, P, depth, G, n_ops):
     lines, want = [f"{P} {depth} {G}"], []
     groups = []
     next_ctx = [1]
+    p_request = 0.45 if depth <= 4 else 0.8  # (a deep ring fills only under more requests than acks)
     for g in range(G):
         cfg = random_cfg(rng, P)
         lo = rng.randint(1, 5)
@@ -256,7 +257,7 @@ def make_script(seed, P, depth, G, n_ops):
             for _ in range(rng.choice([1, 1, 1, 2, 3, 4])):
                 pend = [c for c, _, _ in grp.queue()]
                 k = rng.random()
-                if k < 0.45:
+                if k < p_request:
                     if pend and rng.random() < 0.25:
                         ctx = rng.choice(pend)  # a duplicate
                     else:
@@ -295,14 +296,17 @@ def make_script(seed, P, depth, G, n_ops):
     return "\n".join(lines) + "\n", "\n".join(want) + "\n", ops
 
 
-CASES = [(P, depth) for P in range(1, 9) for depth in (1, 2, 4)]
+# (depth 7: the ring wraps at a size that is no power of two; depth 16: RG_READ_MAX_DEPTH, the whole RgReadCopy)
+CASES = [(P, depth) for P in range(1, 9) for depth in (1, 2, 4, 7, 16)]
 
 
 def run_twin(exe, tmp_path, n_per_case):
     total = 0
-    seen = set()
+    seen, full_at = set(), set()
     for k, (P, depth) in enumerate(CASES):
-        script, want, ops = make_script(1000 + k, P, depth, 12, n_per_case)
+        # (the cases of depth 1, 2 and 4 keep the seeds they had before depths 7 and 16 joined them)
+        seed = 1000 + (P - 1) * 3 + (1, 2, 4).index(depth) if depth <= 4 else 2000 + k
+        script, want, ops = make_script(seed, P, depth, 12, n_per_case)
         path = tmp_path / f"script_{P}_{depth}.txt"
         path.write_text(script)
         r = subprocess.run([exe, str(path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
@@ -315,21 +319,24 @@ def run_twin(exe, tmp_path, n_per_case):
         for line in want.split("\n"):
             if line.startswith("s "):
                 seen |= set(line.split()[1:])
-    return total, seen
+                if str(M.FULL) in line.split()[1:]:
+                    full_at.add(depth)
+    return total, seen, full_at
 
 
 def test_host_twin_matches_the_model(tmp_path):
-    """>= 200 000 seeded random operations over P = 1..8 x depth 1, 2, 4: joint configurations, learners, singletons, voters
+    """>= 200 000 seeded random operations over P = 1..8 x depth 1, 2, 4, 7, 16: joint configurations, learners, singletons, voters
     without a Progress, term bumps, configuration changes followed by the re-check, duplicates, unknown contexts, absent slots.
     Statuses, emitted states and final queues must be the model's, line for line."""
     exe = build_twin(tmp_path, "read_twin", [])
-    total, seen = run_twin(exe, tmp_path, 8500)
+    total, seen, full_at = run_twin(exe, tmp_path, 8500)
     assert total >= 200000
+    assert full_at == {1, 2, 4, 7, 16}  # every ring was full at some point, the deepest included
     assert seen == {str(s) for s in (M.NOT_READY, M.READY, M.QUEUED, M.DUPLICATE, M.FULL)}
 
 
 def test_host_twin_is_clean_under_asan_and_ubsan(tmp_path):
     """The same program, -fsanitize=address,undefined -fno-sanitize-recover=all, run directly (a stand-alone executable)."""
     exe = build_twin(tmp_path, "read_twin_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"])
-    total, _ = run_twin(exe, tmp_path, 1500)
-    assert total >= 24 * 1500
+    total, _, full_at = run_twin(exe, tmp_path, 1500)
+    assert total >= len(CASES) * 1500 and full_at == {1, 2, 4, 7, 16}
