@@ -848,7 +848,13 @@ int rg_mailbox_stats(const rg_engine *h, uint64_t *flushes_served, uint64_t *lau
  * (LDS-staged AoS->SoA transpose) and collects the set of touched groups; rg_tick_ingested runs the same
  * per-group arithmetic as rg_tick over exactly those groups and consumes the events. At most ONE record per
  * (group, slot) between two rg_tick_ingested calls: a second one is dropped and counted in n_duplicates (the
- * caller re-submits it after the tick, which preserves per-peer order). rg_flush uses this path. */
+ * caller re-submits it after the tick, which preserves per-peer order). rg_flush uses this path.
+ * Ingested records stay pending until the next rg_tick_ingested / rg_ingest_tick / rg_flush, which applies them to the
+ * state as it then is: rg_recompute, rg_checkpoint / rg_restore and rg_tick_device in between leave them alone, while
+ * rg_tick / rg_tick_send (whose host columns are staged where the records wait; an rg_flush of half the groups or more
+ * is one) and rg_permute_groups are refused with RG_ERR_STATE until they are ticked.
+ * Dropped records (duplicates and malformed ones) are counted per window: rg_ingest reports the drops of its OWN call,
+ * rg_ingested_duplicates and rg_ingest_tick those of the whole window so far. */
 typedef struct {
     uint64_t group;  /* engine-local group index */
     uint64_t index;  /* Message.index (self slot: persisted index) */
@@ -862,8 +868,8 @@ typedef struct {
 } rg_wire_msg;
 int rg_ingest(rg_engine *h, const rg_wire_msg *host_records, uint64_t n, uint64_t *n_duplicates);
 /* Same, records already in DEVICE memory (a device-side transport / decoder); the array must hold
- * n records (any alignment of 16 B). Asynchronous: duplicates are accumulated and reported by the next
- * rg_ingest (host) call or readable through rg_ingested_duplicates after rg_sync. */
+ * n records (any alignment of 16 B). Asynchronous: its drops are accumulated in the window's count, which
+ * rg_ingested_duplicates reads and the window's rg_ingest_tick returns (a later rg_ingest reports only its own). */
 int rg_ingest_device(rg_engine *h, const rg_wire_msg *dev_records, uint64_t n);
 int rg_ingested_duplicates(rg_engine *h, uint64_t *n_duplicates);
 int rg_tick_ingested(rg_engine *h, uint64_t *n_groups);

@@ -48,10 +48,8 @@ int rg_ensure_sparse(rg_engine *h) {
     return RG_OK;
 }
 
-extern "C" int rg_ingest(rg_engine *h, const rg_wire_msg *records, uint64_t n, uint64_t *n_duplicates) try {
-    if (!h || (!records && n)) return rg_fail(RG_ERR_INVALID_ARG, "rg_ingest: bad argument");
-    if (n_duplicates) *n_duplicates = 0;
-    if (n == 0) return RG_OK;
+// rg_ingest; *call_dups: records of THIS call that were dropped, *window_dups: those of the whole window so far
+static int rg_ingest_impl(rg_engine *h, const rg_wire_msg *records, u64 n, u64 *call_dups, u64 *window_dups) {
     RG_ENTER_STEP(h, "rg_ingest");
     int rc = rg_ensure_sparse(h);
     if (rc) return rc;
@@ -74,9 +72,17 @@ extern "C" int rg_ingest(rg_engine *h, const rg_wire_msg *records, uint64_t n, u
     u32 dup = 0;
     RG_HIP(hipMemcpyAsync(&dup, h->counters + 1, 4, hipMemcpyDeviceToHost, h->stream));
     RG_HIP(hipStreamSynchronize(h->stream)); // the caller's record array may be reused after return
-    if (n_duplicates) *n_duplicates = dup - dup0; // dup0 was read before the kernel ran (stream order)
+    if (call_dups) *call_dups = dup - dup0; // dup0 was read before the kernel ran (stream order)
+    if (window_dups) *window_dups = dup;
     h->ingested_upper += n;
     return RG_OK;
+}
+
+extern "C" int rg_ingest(rg_engine *h, const rg_wire_msg *records, uint64_t n, uint64_t *n_duplicates) try {
+    if (!h || (!records && n)) return rg_fail(RG_ERR_INVALID_ARG, "rg_ingest: bad argument");
+    if (n_duplicates) *n_duplicates = 0;
+    if (n == 0) return RG_OK;
+    return rg_ingest_impl(h, records, n, n_duplicates, nullptr);
 } RG_ABI_GUARD
 
 extern "C" int rg_ingest_device(rg_engine *h, const rg_wire_msg *dev_records, uint64_t n) try {
@@ -477,8 +483,11 @@ struct rg_send_req { // run the send stage inside the same round trip (engines w
 static int rg_sparse_threecall(rg_engine *h, const rg_wire_msg *recs, u64 n, u32 *dup_out, const rg_send_req *send) {
     // big batches are throughput-bound, not latency-bound: the packed copy (one slot per RECORD, not per group)
     // and the host-side unpacking cost more than two extra synchronisations (profiles/r01_sparse_path...)
-    uint64_t d64 = 0, ng = 0;
-    int rc = rg_ingest(h, recs, n, &d64);
+    // (the drops of the WHOLE window, device-side ingests included, as on the round-trip roads: read behind this call's
+    // ingest kernel, before the tick flips the counter pair)
+    u64 d64 = 0;
+    uint64_t ng = 0;
+    int rc = rg_ingest_impl(h, recs, n, nullptr, &d64);
     if (rc == RG_OK) rc = rg_tick_ingested(h, &ng);
     if (rc == RG_OK && send) rc = rg_send_appends(h, send->max_entries, send->flags);
     if (dup_out) *dup_out = (u32)d64;

@@ -437,6 +437,9 @@ int rg_ensure_msg_arena(rg_engine *h) {
 
 int rg_tick_host_impl(rg_engine *h, const rg_msgs *m, const RgSendReq *send) {
     RG_ENTER_STEP(h, "rg_tick");
+    // pending records live in the engine-owned message columns this tick stages its host columns in: it would wipe them
+    if (h->ingested_upper)
+        return rg_fail(RG_ERR_STATE, "rg_tick: records are ingested and not ticked yet (rg_ingest): tick them first");
     int rc = rg_ensure_msg_arena(h);
     if (rc) return rc;
     const size_t colb = (size_t)h->P * h->stride * 8;

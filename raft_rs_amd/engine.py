@@ -580,8 +580,19 @@ class Engine:
         self._check(self.L.rg_ingest_tick(self.h, rec.ctypes.data, len(rec), C.byref(n), C.byref(dup)))
         return n.value, dup.value
 
-    def ingested_results(self):
+    def ingested_results(self, cap=None):
+        """(groups, commit, out) of the last sparse tick. cap: hand rg_ingested_results arrays of that capacity instead of
+        asking for the count first -> (groups, commit, out, n): arrays of length cap of which min(cap, n) are written
+        (the rest keeps its 0xA5 fill), n the true count."""
         n = _u64(0)
+        if cap is not None:
+            groups = np.full(cap, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+            commit = np.full(cap, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+            out = np.full(cap, 0xA5A5A5A5, dtype=np.uint32)
+            self._check(self.L.rg_ingested_results(self.h, groups.ctypes.data if cap else None,
+                                                   commit.ctypes.data if cap else None, out.ctypes.data if cap else None,
+                                                   cap, C.byref(n)))
+            return groups, commit, out, n.value
         self._check(self.L.rg_ingested_results(self.h, None, None, None, 0, C.byref(n)))
         k = n.value
         groups = np.empty(k, dtype=np.uint64)
