@@ -477,7 +477,9 @@ int rg_maximal_committed_index(rg_engine *h, uint64_t *host_mci, uint8_t *host_u
 /* Raft::bcast_heartbeat (src/raft.rs:885-891 -> send_heartbeat :822-844): the commit index each
  * MsgHeartbeat carries, min(pr.matched, raft_log.committed), for every slot -> u64 [P][stride] in DEVICE
  * memory (`dev_hb_commit`) or, when `host_hb_commit` is not NULL, copied to the host. Slots without a
- * Progress get 0. Asynchronous unless a host destination is given. */
+ * Progress get 0. Only the cells of groups 0 .. G-1 of each row are written: the padding cells [G, stride) of a device
+ * destination keep what they held, those of a host destination are unspecified. Asynchronous unless a host destination is
+ * given. */
 int rg_heartbeat_commits(rg_engine *h, uint64_t *dev_hb_commit, uint64_t *host_hb_commit);
 /* Results of the last tick: commit[G] and out[G] to host memory (either may be NULL). Synchronises. */
 int rg_results(rg_engine *h, uint64_t *host_commit, uint32_t *host_out);
@@ -514,9 +516,13 @@ typedef struct {
 } rg_resolved_hint;
 int rg_resolve_host_hints(rg_engine *h, const rg_resolved_hint *items, uint64_t n, uint8_t *host_applied);
 
-/* Census of a tick's message flags in DEVICE memory: counts[0] = VALID messages, [1] = rejects,
- * [2] = slots with a Progress, [3] = groups with at least one event, [4] = RG_MF_BECOME_LEADER events
- * (bench: algorithmic bytes, rejects and elections per group). */
+/* Census of a tick's message flags (u8 [G][8]) in DEVICE memory: counts[0] = VALID messages (flag bytes with RG_MF_VALID),
+ * [1] = rejects (bytes with RG_MF_VALID and RG_MF_REJECT both, on slots other than the group's self slot, where that bit is
+ * RG_MF_BECOME_LEADER), [2] = slots with a Progress (RG_CFG_PRESENT), [3] = groups with at least one event (a non-zero flag
+ * byte), [4] = RG_MF_BECOME_LEADER events (the bit on the self slot of a group whose self slot has a Progress; RG_MF_VALID is
+ * not needed, as for the tick) (bench: algorithmic bytes, rejects and elections per group). The census does not know the
+ * engine's slot count: it reads all 8 flag bytes of a group, so a caller that wants the census of its n_slots slots
+ * keeps the bytes of slots >= n_slots zero; bits there are counted in [0], [1] and [3] like any other slot's. Synchronises. */
 int rg_msg_stats(rg_engine *h, const uint8_t *dev_m_flags, uint64_t counts[5]);
 
 /* ---- vote / quorum-liveness bitmaps (src/quorum/majority.rs:130-154, src/quorum/joint.rs:56-67,

@@ -127,7 +127,7 @@ struct rg_engine {
     char *msg_arena;  // device staging for rg_tick(host msgs) / rg_flush (lazy)
     u64 *zero_col;    // [P][stride] zeros, substituted for NULL m_hint / m_rs
     u64 *rhint;       // [P][stride] reject hints after find_conflict_by_term (pre-pass output)
-    u64 *d_counts;    // 4 x u64 scratch for reductions
+    u64 *d_counts;    // scratch for reductions: up to 5 x u64 (rg_msg_stats) of the 256 bytes set aside in rg_create
     void *d_scratch;  // G x 8 B scratch for host<->device result shuttles
     size_t col_off[RG_COL_COUNT];
     RgState st;

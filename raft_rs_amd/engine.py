@@ -756,8 +756,12 @@ class Engine:
         self._check(self.L.rg_maximal_committed_index(self.h, mci.ctypes.data, _ptr(gc)))
         return (mci, gc) if with_flag else mci
 
-    def heartbeat_commits(self):
-        """bcast_heartbeat: min(matched, committed) per slot -> [P][stride] u64 (host copy)."""
+    def heartbeat_commits(self, dev_out=None):
+        """bcast_heartbeat: min(matched, committed) per slot -> [P][stride] u64 (host copy). dev_out: a DEVICE pointer to
+        u64 [P][stride] that receives the column instead (asynchronous on the engine's stream; returns None)."""
+        if dev_out is not None:
+            self._check(self.L.rg_heartbeat_commits(self.h, _ptr(dev_out), None))
+            return None
         hb = np.empty((self.n_slots, self.stride), dtype=np.uint64)
         self._check(self.L.rg_heartbeat_commits(self.h, None, hb.ctypes.data))
         return hb
@@ -801,9 +805,15 @@ class Engine:
         self.permute_groups(perm)
         return perm, classes
 
-    def host_hints(self):
-        """Groups whose last tick raised RG_OUT_HOST_HINT -> HOST_HINT_DTYPE array (group, slot_mask)."""
+    def host_hints(self, cap=None):
+        """Groups whose last tick raised RG_OUT_HOST_HINT -> HOST_HINT_DTYPE array (group, slot_mask). cap: hand rg_host_hints an
+        array of that capacity (cap = 0: no array at all) instead of asking again -> (items, n): an array of length cap of which
+        min(cap, n) entries are written (the rest keeps its 0xA5 fill), n the true count."""
         n = _u64(0)
+        if cap is not None:
+            items = np.frombuffer(bytes([0xA5]) * (cap * HOST_HINT_DTYPE.itemsize), dtype=HOST_HINT_DTYPE).copy()
+            self._check(self.L.rg_host_hints(self.h, items.ctypes.data if cap else None, cap, C.byref(n)))
+            return items, n.value
         items = np.zeros(256, dtype=HOST_HINT_DTYPE)
         self._check(self.L.rg_host_hints(self.h, items.ctypes.data, len(items), C.byref(n)))
         if n.value > len(items):
