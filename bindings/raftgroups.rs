@@ -5,7 +5,7 @@
 use std::os::raw::{c_char, c_void};
 
 pub const RG_MAX_SLOTS: u32 = 8;
-pub const RG_ABI_VERSION: u32 = 8;
+pub const RG_ABI_VERSION: u32 = 9;
 pub const RG_PF_STATE_MASK: u32 = 0x03;
 pub const RG_STATE_PROBE: u32 = 0;
 pub const RG_STATE_REPLICATE: u32 = 1;
@@ -66,6 +66,16 @@ pub const RG_READ_QUEUED: u32 = 2;
 pub const RG_READ_DUPLICATE: u32 = 3;
 pub const RG_READ_FULL: u32 = 4;
 pub const RG_READ_ACK_LAST_SELF: u32 = 0x1;
+pub const RG_FOLLOW_RUNS: u32 = 9;
+pub const RG_FOLLOW_MSG_APPEND: u32 = 0x1;
+pub const RG_FOLLOW_MSG_HEARTBEAT: u32 = 0x2;
+pub const RG_FOLLOW_NONE: u32 = 0;
+pub const RG_FOLLOW_ACCEPT: u32 = 1;
+pub const RG_FOLLOW_REJECT: u32 = 2;
+pub const RG_FOLLOW_STALE: u32 = 3;
+pub const RG_FOLLOW_HEARTBEAT: u32 = 4;
+pub const RG_FOLLOW_FAULT: u32 = 5;
+pub const RG_FOLLOW_HOST: u32 = 6;
 pub const RG_SEND_APPEND: u32 = 1;
 pub const RG_SEND_SNAPSHOT: u32 = 2;
 pub const RG_SEND_HOST: u32 = 3;
@@ -249,6 +259,72 @@ pub struct RgReadState {
     pub group: u64,
     pub ctx: u64,
     pub index: u64,
+}
+
+#[repr(C)]
+pub struct RgFollowState {
+    pub group: u64,
+    pub committed: u64,
+    pub last_index: u64,
+    pub dummy_index: u64,
+    pub dummy_term: u64,
+    pub n_runs: u32,
+    pub reserved: u32,
+    pub run_first: [u64; RG_FOLLOW_RUNS as usize],
+    pub run_term: [u64; RG_FOLLOW_RUNS as usize],
+}
+
+#[repr(C)]
+pub struct RgFollowEntRun {
+    pub term: u64,
+    pub count: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+pub struct RgFollowMsg {
+    pub group: u64,
+    pub index: u64,
+    pub log_term: u64,
+    pub commit: u64,
+    pub ent_term: u64,
+    pub n_entries: u32,
+    pub flags: u32,
+    pub ext: u64,
+}
+
+#[repr(C)]
+pub struct RgFollowResp {
+    pub index: u64,
+    pub commit: u64,
+    pub conflict: u64,
+    pub reject_hint: u64,
+    pub log_term: u64,
+    pub status: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+pub struct RgFollowMsgs {
+    pub flags: *const u8,
+    pub index: *const u64,
+    pub log_term: *const u64,
+    pub commit: *const u64,
+    pub ent_term: *const u64,
+    pub n_entries: *const u32,
+    pub ext: *const u64,
+    pub ext_runs: *const RgFollowEntRun,
+    pub n_ext: u64,
+}
+
+#[repr(C)]
+pub struct RgFollowOut {
+    pub status: *mut u8,
+    pub index: *mut u64,
+    pub commit: *mut u64,
+    pub conflict: *mut u64,
+    pub reject_hint: *mut u64,
+    pub log_term: *mut u64,
 }
 
 #[repr(C)]
@@ -474,6 +550,12 @@ extern "C" {
     pub fn rg_read_states(h: *mut RgEngine, host_items: *mut RgReadState, cap: u64, n: *mut u64) -> i32;
     pub fn rg_read_last_pending(h: *mut RgEngine, dev_ctx_g: *mut u64, host_ctx_g: *mut u64) -> i32;
     pub fn rg_read_pending_counts(h: *mut RgEngine, host_counts: *mut u8) -> i32;
+    pub fn rg_follow_enable(h: *mut RgEngine, n_follow: u64) -> i32;
+    pub fn rg_follow_stride(h: *const RgEngine) -> u64;
+    pub fn rg_follow_write(h: *mut RgEngine, host_states: *const RgFollowState, n: u64) -> i32;
+    pub fn rg_follow_read(h: *mut RgEngine, host_groups: *const u64, n: u64, host_out: *mut RgFollowState) -> i32;
+    pub fn rg_follow_step(h: *mut RgEngine, host_msgs: *const RgFollowMsg, n: u64, host_ext: *const RgFollowEntRun, n_ext: u64, host_resp: *mut RgFollowResp) -> i32;
+    pub fn rg_follow_step_device(h: *mut RgEngine, dev_msgs: *const RgFollowMsgs, dev_out: *const RgFollowOut) -> i32;
     pub fn rg_set_peers(h: *mut RgEngine, group: u64, peer_ids: *const u64, n: u32, term: u64) -> i32;
     pub fn rg_step(h: *mut RgEngine, group: u64, m: *const RgAppendResponse) -> i32;
     pub fn rg_step_heartbeat_response(h: *mut RgEngine, group: u64, from: u64, term: u64, commit: u64, ins_full: u8) -> i32;

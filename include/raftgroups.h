@@ -41,7 +41,7 @@ extern "C" {
  * new members keep the old meaning), so a caller is compiled against the header of the library it loads. RG_ABI_VERSION is bumped
  * whenever a struct layout, an enum value or a signature changes; rg_abi_version() returns what the library was built with --
  * compare the two at start-up (raftgroups.hpp and the Python / Rust bindings do). */
-#define RG_ABI_VERSION 8u
+#define RG_ABI_VERSION 9u
 
 /* ---- status codes; the negative values mirror src/errors.rs:6-50 where one applies ----
  * Every entry point that returns int returns one of these and leaves the text in rg_last_error() (per thread). Nothing unwinds
@@ -609,6 +609,106 @@ int rg_read_states(rg_engine *h, rg_read_state *host_items, uint64_t cap, uint64
 int rg_read_last_pending(rg_engine *h, uint64_t *dev_ctx_g, uint64_t *host_ctx_g);
 /* ReadOnly::pending_read_count (src/read_only.rs:136-139) of every group -> host u8 [G]. Synchronises. */
 int rg_read_pending_counts(rg_engine *h, uint8_t *host_counts);
+
+/* ---- The follower half: MsgAppend and MsgHeartbeat steps (Raft::handle_append_entries, src/raft.rs:2389-2448;
+ *      Raft::handle_heartbeat, src/raft.rs:2452-2464; RaftLog::maybe_append / find_conflict / find_conflict_by_term / commit_to,
+ *      src/raft_log.rs:182-300) ----
+ * For the groups a store FOLLOWS, the device holds the integer summary of the RaftLog in an arena of its own (its own index
+ * space: n_follow is independent of rg_config.n_groups; no tick, flush, publication or rg_permute_groups touches it):
+ * committed, last_index, the dummy entry (first_index - 1 and its term), and the log's terms as runs of equal-term entries in
+ * ascending order -- at most RG_TERM_RUNS older runs plus the tail run that ends at last_index. Filing a ninth older run drops
+ * the oldest (as the leader side's table does); the terms of (dummy_index, first known index) are then NOT on the device.
+ *   Entries are described, not shipped: an entry list is runs of (term, count) with consecutive indices from index + 1. Run 0
+ *   is inline in the record, further runs come from a side array. Runs with count 0 are skipped.
+ *   MsgAppend {index, log_term, commit, entries}, from src/raft.rs:2394 on (the host does not pass records of a group whose
+ *   pending_request_snapshot is set):
+ *     RG_FOLLOW_STALE   index < committed: {index = committed, commit = committed}; nothing changes, no term is looked at.
+ *     RG_FOLLOW_ACCEPT  match_term(index, log_term) (term() = 0 outside [dummy_index, last_index]): conflict =
+ *                       find_conflict(entries); if it is not 0 the log is cut to conflict - 1 and the entries from `conflict` on
+ *                       become its tail; commit_to(min(commit, index + n)). {index = index + n, commit = committed, conflict}:
+ *                       the host writes entries[conflict - index - 1 ..] and lowers `persisted` (src/raft_log.rs:270-272).
+ *     RG_FOLLOW_REJECT  otherwise: find_conflict_by_term(min(index, last_index), log_term).
+ *                       {index = m.index, reject_hint, log_term = term(reject_hint), commit = committed}.
+ *   MsgHeartbeat {commit}: commit_to(commit). RG_FOLLOW_HEARTBEAT {commit = committed}.
+ *   RG_FOLLOW_FAULT: the record is NOT applied, the group's state is untouched, later records of the group still run. Raised
+ *     where the reference panics -- conflict <= committed (src/raft_log.rs:259-265), commit_to beyond last_index (:291-298), an
+ *     append that would leave a hole behind last_index (src/log_unstable.rs:169) -- and where index + n reaches 2^63. It is
+ *     ALSO raised where the reference appends malformed entries and this engine refuses to: the device's log must stay
+ *     monotone in its terms, so entries whose terms decrease from the conflict point on, or whose first appended term is below
+ *     term(conflict - 1), are refused loudly. The dense call also answers FAULT to a record whose flags are not exactly one
+ *     kind or whose `ext` points outside the side array (the sparse call refuses those on the host).
+ *   RG_FOLLOW_HOST: not applied, state untouched: the evaluation needs the term of an entry in the dropped gap and
+ *     monotonicity does not settle it. A gap entry's term is some value of [dummy_term, first known term]; a comparison whose
+ *     outcome is the same for every value of that interval proceeds, any other -- and needing the value itself, as log_term =
+ *     term(reject_hint) of a reject that stops inside the gap -- hands the record back. A log that has seen at most
+ *     RG_TERM_RUNS older terms since its snapshot never raises it. The host handles the message with its own RaftLog and
+ *     re-loads the group with rg_follow_write.
+ *   FAULT and HOST answer {index = m.index, commit = committed}.
+ * The term gate of Raft::step (src/raft.rs:1282-1411), become_follower, election_elapsed, leader_id, snapshots, `persisted` and
+ * turning a response record into a Message stay on the host.
+ * Every call before rg_follow_enable returns RG_ERR_STATE, so does a second enable. rg_checkpoint / rg_restore include the
+ * arena, rg_destroy frees it, rg_device_info.engine_bytes grows by its size. */
+#define RG_FOLLOW_RUNS 9 /* RG_TERM_RUNS older runs + the tail */
+int rg_follow_enable(rg_engine *h, uint64_t n_follow); /* once; allocates the arena: 177 bytes per group of the stride */
+uint64_t rg_follow_stride(const rg_engine *h);         /* n_follow rounded up to 256; 0 before enable */
+typedef struct {
+    uint64_t group, committed, last_index, dummy_index, dummy_term;
+    uint32_t n_runs, reserved; /* 0..RG_FOLLOW_RUNS, ascending; the last run is the tail (0 runs: an empty log) */
+    uint64_t run_first[RG_FOLLOW_RUNS], run_term[RG_FOLLOW_RUNS];
+} rg_follow_state;
+/* Load whole group states (control path; synchronises). RG_ERR_INVALID_ARG, and nothing written, for a group at or beyond
+ * n_follow or a state that is not canonical: run_first not strictly ascending, run_term not strictly ascending or below
+ * dummy_term, run_first[0] <= dummy_index, run_first of the tail > last_index, committed > last_index, committed or last_index
+ * < dummy_index, runs without entries (last_index == dummy_index) or entries without runs, dummy_index 0 with a non-zero term,
+ * last_index >= 2^63. run_first[0] > dummy_index + 1 declares a gap. */
+int rg_follow_write(rg_engine *h, const rg_follow_state *host_states, uint64_t n);
+/* Read whole group states in the same canonical form (unused runs are 0). Synchronises. */
+int rg_follow_read(rg_engine *h, const uint64_t *host_groups, uint64_t n, rg_follow_state *host_out);
+typedef struct {
+    uint64_t term;
+    uint32_t count, reserved;
+} rg_follow_ent_run;
+#define RG_FOLLOW_MSG_APPEND 0x1u
+#define RG_FOLLOW_MSG_HEARTBEAT 0x2u
+typedef struct {
+    uint64_t group, index, log_term, commit, ent_term;
+    uint32_t n_entries; /* of run 0 */
+    uint32_t flags;     /* RG_FOLLOW_MSG_APPEND or RG_FOLLOW_MSG_HEARTBEAT, exactly one */
+    uint64_t ext;       /* (offset << 8) | count of further runs in the side array; 0 = none */
+} rg_follow_msg;
+typedef struct {
+    uint64_t index, commit, conflict, reject_hint, log_term;
+    uint32_t status, reserved;
+} rg_follow_resp;
+#define RG_FOLLOW_NONE 0u
+#define RG_FOLLOW_ACCEPT 1u
+#define RG_FOLLOW_REJECT 2u
+#define RG_FOLLOW_STALE 3u
+#define RG_FOLLOW_HEARTBEAT 4u
+#define RG_FOLLOW_FAULT 5u
+#define RG_FOLLOW_HOST 6u
+/* Sparse: n records, any groups, several per group allowed -- applied per group in array order; host_resp[i] answers
+ * host_msgs[i]. RG_ERR_INVALID_ARG, and nothing applied, for a group at or beyond n_follow, flags that are not exactly one
+ * kind, or an ext outside host_ext[n_ext]. Synchronises. */
+int rg_follow_step(rg_engine *h, const rg_follow_msg *host_msgs, uint64_t n, const rg_follow_ent_run *host_ext, uint64_t n_ext,
+                   rg_follow_resp *host_resp);
+/* Dense: one record per follower group, struct-of-arrays in DEVICE memory, [rg_follow_stride] each; flags[g] == 0 = no
+ * message. ext / ext_runs may be NULL (every message single-term). status[g] is written for every group (0 = no message);
+ * index, commit and conflict only where status != 0; reject_hint and log_term only on rejects. Asynchronous on the engine's
+ * stream. */
+typedef struct {
+    const uint8_t *flags;
+    const uint64_t *index, *log_term, *commit, *ent_term;
+    const uint32_t *n_entries;
+    const uint64_t *ext;
+    const rg_follow_ent_run *ext_runs;
+    uint64_t n_ext;
+} rg_follow_msgs;
+typedef struct {
+    uint8_t *status;
+    uint64_t *index, *commit, *conflict, *reject_hint, *log_term;
+} rg_follow_out;
+int rg_follow_step_device(rg_engine *h, const rg_follow_msgs *dev_msgs, const rg_follow_out *dev_out);
 
 /* ---- message-at-a-time host mirror of RawNode::step for MsgAppendResponse
  *      (src/raw_node.rs:402-411 -> src/raft.rs:1280-1411 term gate -> :2096-2098) ---- */

@@ -184,6 +184,7 @@ extern "C" int rg_create(const rg_config *cfg, rg_engine **out) try {
     h->ins_ckpt = nullptr;
     h->esz = h->esz_ckpt = nullptr;
     h->rd = nullptr;
+    h->fo = nullptr;
     h->d_recs = nullptr;
     h->d_recs_cap = 0;
     h->mbox = nullptr;
@@ -403,6 +404,7 @@ extern "C" void rg_destroy(rg_engine *h) {
     if (h->esz) (void)hipFree(h->esz);
     if (h->esz_ckpt) (void)hipFree(h->esz_ckpt);
     rg_read_free(h);
+    rg_follow_free(h);
     if (h->d_recs) (void)hipFree(h->d_recs);
     if (h->msg_arena) (void)hipFree(h->msg_arena);
     if (h->sparse_arena) (void)hipFree(h->sparse_arena);
@@ -516,6 +518,8 @@ extern "C" int rg_checkpoint(rg_engine *h) try {
         if (!h->esz_ckpt) RG_HIP(hipMalloc(&h->esz_ckpt, b));
         RG_HIP(hipMemcpyAsync(h->esz_ckpt, h->esz, b, hipMemcpyDeviceToDevice, h->stream));
     }
+    const int frc = rg_follow_checkpoint(h); // (the follower arena, if enabled)
+    if (frc) return frc;
     return rg_read_checkpoint(h); // (the pending-read queues, if enabled)
 } RG_ABI_GUARD
 
@@ -542,6 +546,8 @@ extern "C" int rg_restore(rg_engine *h) try {
     }
     if (h->esz && h->esz_ckpt)
         RG_HIP(hipMemcpyAsync(h->esz, h->esz_ckpt, (size_t)h->G * h->ins.esz_w * 4, hipMemcpyDeviceToDevice, h->stream));
+    const int frc = rg_follow_restore(h);
+    if (frc) return frc;
     return rg_read_restore(h);
 } RG_ABI_GUARD
 

@@ -26,6 +26,7 @@
 #include "rg_wire.h"
 #include "rg_workload.h"
 #include "rg_read.h"
+#include "rg_follow.h"
 
 #include "rg_tick_kernels.h"
 
@@ -111,6 +112,17 @@ struct RgReadEngine {
     std::vector<RgReadRec> recs;
 };
 
+// The follower half (abi_follow.hip): the optional arena of the groups this store follows -- its own index space, absent until
+// rg_follow_enable; no tick, flush, publication or rg_permute_groups touches it.
+struct RgFollowEngine {
+    RgFollowCols cols;
+    char *arena, *ckpt; // the columns of RgFollowCols, [stride] each; the checkpoint copy (lazy)
+    size_t bytes;
+    std::vector<char> stage;             // host staging of one sparse batch / one read
+    std::vector<u32> order;              // ... its records' positions, sorted by group
+    std::vector<rg_follow_state> states; // ... of one rg_follow_write
+};
+
 // ------------------------------------------------------------------------------------------------
 // engine object
 // ------------------------------------------------------------------------------------------------
@@ -162,7 +174,8 @@ struct rg_engine {
     char *ins_ckpt;    // checkpoint copy of meta | ring (lazy)
     u32 *esz, *esz_ckpt; // entry sizes for RG_SEND_BYTES (rg_log_sizes_enable), u32 [G][esz_w]; checkpoint copy (lazy)
     struct RgReadEngine *rd; // ReadIndex: pending-read queues and the list of read states (rg_read_index_enable), nullptr = off
-    void *d_recs;      // staging for rg_log_sizes_write / rg_update_state / rg_read_index records
+    struct RgFollowEngine *fo; // the follower half: the followed groups' log summaries (rg_follow_enable), nullptr = off
+    void *d_recs;      // staging for rg_log_sizes_write / rg_update_state / rg_read_index / rg_follow_* records
     size_t d_recs_cap;
     // resident small-batch path (rg_mailbox_start): request / answer block in pinned host memory, whether the feature is
     // on, whether the host has launched an instance it has not seen leave, the last request number
@@ -306,4 +319,8 @@ int rg_rccl_load();
 void rg_read_free(rg_engine *h);
 int rg_read_checkpoint(rg_engine *h);
 int rg_read_restore(rg_engine *h);
+// abi_follow.hip: the same for the optional follower arena
+void rg_follow_free(rg_engine *h);
+int rg_follow_checkpoint(rg_engine *h);
+int rg_follow_restore(rg_engine *h);
 

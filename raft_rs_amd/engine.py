@@ -206,7 +206,7 @@ class PublishStats(C.Structure):
                 ("events_on_tick_packets", C.c_uint64)]
 
 
-ABI_VERSION = 8  # RG_ABI_VERSION of include/raftgroups.h these ctypes layouts mirror (tests/test_abi.py compares)
+ABI_VERSION = 9  # RG_ABI_VERSION of include/raftgroups.h these ctypes layouts mirror (tests/test_abi.py compares)
 class CommInfo(C.Structure):
     _fields_ = [("rank", C.c_uint32), ("world", C.c_uint32), ("transport", C.c_uint32), ("in_process", C.c_uint32),
                 ("rccl_ranks", C.c_uint32), ("rccl_rank", C.c_uint32)]
@@ -235,6 +235,30 @@ READ_LEASE = 1
 READ_ACK_LAST_SELF = 1
 READ_NOT_READY, READ_READY, READ_QUEUED, READ_DUPLICATE, READ_FULL = 0, 1, 2, 3, 4
 READ_MAX_DEPTH = 16
+# The follower half (rg_follow_enable ...)
+FOLLOW_RUNS = 9
+FOLLOW_STATE_DTYPE = np.dtype([("group", "<u8"), ("committed", "<u8"), ("last_index", "<u8"), ("dummy_index", "<u8"), ("dummy_term", "<u8"),
+                               ("n_runs", "<u4"), ("reserved", "<u4"), ("run_first", "<u8", (FOLLOW_RUNS,)),
+                               ("run_term", "<u8", (FOLLOW_RUNS,))])                                # rg_follow_state
+FOLLOW_ENT_RUN_DTYPE = np.dtype([("term", "<u8"), ("count", "<u4"), ("reserved", "<u4")])           # rg_follow_ent_run
+FOLLOW_MSG_DTYPE = np.dtype([("group", "<u8"), ("index", "<u8"), ("log_term", "<u8"), ("commit", "<u8"), ("ent_term", "<u8"),
+                             ("n_entries", "<u4"), ("flags", "<u4"), ("ext", "<u8")])               # rg_follow_msg
+FOLLOW_RESP_DTYPE = np.dtype([("index", "<u8"), ("commit", "<u8"), ("conflict", "<u8"), ("reject_hint", "<u8"), ("log_term", "<u8"),
+                              ("status", "<u4"), ("reserved", "<u4")])                              # rg_follow_resp
+assert (FOLLOW_STATE_DTYPE.itemsize, FOLLOW_ENT_RUN_DTYPE.itemsize, FOLLOW_MSG_DTYPE.itemsize, FOLLOW_RESP_DTYPE.itemsize) == (192, 16, 56, 48)
+FOLLOW_MSG_APPEND, FOLLOW_MSG_HEARTBEAT = 1, 2
+FOLLOW_NONE, FOLLOW_ACCEPT, FOLLOW_REJECT, FOLLOW_STALE, FOLLOW_HEARTBEAT, FOLLOW_FAULT, FOLLOW_HOST = 0, 1, 2, 3, 4, 5, 6
+
+
+class FollowMsgs(C.Structure):  # rg_follow_msgs: device pointers
+    _fields_ = [("flags", C.c_void_p), ("index", C.c_void_p), ("log_term", C.c_void_p), ("commit", C.c_void_p), ("ent_term", C.c_void_p),
+                ("n_entries", C.c_void_p), ("ext", C.c_void_p), ("ext_runs", C.c_void_p), ("n_ext", C.c_uint64)]
+
+
+class FollowOut(C.Structure):  # rg_follow_out: device pointers
+    _fields_ = [("status", C.c_void_p), ("index", C.c_void_p), ("commit", C.c_void_p), ("conflict", C.c_void_p),
+                ("reject_hint", C.c_void_p), ("log_term", C.c_void_p)]
+
 
 # every symbol include/raftgroups.h declares: (restype, argtypes)
 _vp, _u64, _i = C.c_void_p, C.c_uint64, C.c_int
@@ -308,6 +332,12 @@ SYMBOLS = {
     "rg_read_states": (_i, [_vp, _vp, _u64, C.POINTER(_u64)]),
     "rg_read_last_pending": (_i, [_vp, _vp, _vp]),
     "rg_read_pending_counts": (_i, [_vp, _vp]),
+    "rg_follow_enable": (_i, [_vp, _u64]),
+    "rg_follow_stride": (_u64, [_vp]),
+    "rg_follow_write": (_i, [_vp, _vp, _u64]),
+    "rg_follow_read": (_i, [_vp, _vp, _u64, _vp]),
+    "rg_follow_step": (_i, [_vp, _vp, _u64, _vp, _u64, _vp]),
+    "rg_follow_step_device": (_i, [_vp, C.POINTER(FollowMsgs), C.POINTER(FollowOut)]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -899,6 +929,47 @@ class Engine:
         counts = np.empty(self.n_groups, dtype=np.uint8)
         self._check(self.L.rg_read_pending_counts(self.h, counts.ctypes.data))
         return counts
+
+    # ---- the follower half: MsgAppend / MsgHeartbeat steps of the groups this store follows ---------
+    def follow_enable(self, n_follow):
+        """rg_follow_enable: the arena of n_follow followed groups (an index space of its own). Once."""
+        self._check(self.L.rg_follow_enable(self.h, n_follow))
+
+    def follow_stride(self):
+        return self.L.rg_follow_stride(self.h)
+
+    def follow_write(self, states):
+        """Load whole group states: a FOLLOW_STATE_DTYPE array (canonical, or EngineError)."""
+        states = np.ascontiguousarray(states, dtype=FOLLOW_STATE_DTYPE)
+        self._check(self.L.rg_follow_write(self.h, states.ctypes.data, len(states)))
+
+    def follow_read(self, groups):
+        """Whole group states of `groups` -> FOLLOW_STATE_DTYPE array."""
+        groups = np.ascontiguousarray(groups, dtype=np.uint64)
+        out = np.zeros(len(groups), dtype=FOLLOW_STATE_DTYPE)
+        self._check(self.L.rg_follow_read(self.h, groups.ctypes.data, len(groups), out.ctypes.data))
+        return out
+
+    def follow_step(self, msgs, ext=None):
+        """Sparse step: msgs is a FOLLOW_MSG_DTYPE array (any groups, array order per group), ext a FOLLOW_ENT_RUN_DTYPE array
+        of the further entry runs -> FOLLOW_RESP_DTYPE array, positional."""
+        msgs = np.ascontiguousarray(msgs, dtype=FOLLOW_MSG_DTYPE)
+        n_ext = 0 if ext is None else len(ext)
+        if n_ext:
+            ext = np.ascontiguousarray(ext, dtype=FOLLOW_ENT_RUN_DTYPE)
+        resp = np.zeros(len(msgs), dtype=FOLLOW_RESP_DTYPE)
+        self._check(self.L.rg_follow_step(self.h, msgs.ctypes.data, len(msgs), ext.ctypes.data if n_ext else None, n_ext, resp.ctypes.data))
+        return resp
+
+    def follow_step_device(self, msgs, out):
+        """Dense step (asynchronous): msgs / out are dicts of DEVICE pointers (ints or objects with data_ptr()) named as the
+        fields of rg_follow_msgs / rg_follow_out; msgs may leave out ext / ext_runs / n_ext."""
+        def p(x):
+            return None if x is None else int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+        m = FollowMsgs(*[p(msgs.get(k)) for k in ("flags", "index", "log_term", "commit", "ent_term", "n_entries", "ext", "ext_runs")],
+                       int(msgs.get("n_ext", 0)))
+        o = FollowOut(*[p(out.get(k)) for k in ("status", "index", "commit", "conflict", "reject_hint", "log_term")])
+        self._check(self.L.rg_follow_step_device(self.h, C.byref(m), C.byref(o)))
 
     # ---- message-at-a-time mirror of RawNode::step -----------------------------------------------
     def set_peers(self, group, peer_ids, term):
