@@ -5,7 +5,7 @@
 use std::os::raw::{c_char, c_void};
 
 pub const RG_MAX_SLOTS: u32 = 8;
-pub const RG_ABI_VERSION: u32 = 9;
+pub const RG_ABI_VERSION: u32 = 10;
 pub const RG_PF_STATE_MASK: u32 = 0x03;
 pub const RG_STATE_PROBE: u32 = 0;
 pub const RG_STATE_REPLICATE: u32 = 1;
@@ -76,6 +76,23 @@ pub const RG_FOLLOW_STALE: u32 = 3;
 pub const RG_FOLLOW_HEARTBEAT: u32 = 4;
 pub const RG_FOLLOW_FAULT: u32 = 5;
 pub const RG_FOLLOW_HOST: u32 = 6;
+pub const RG_GATE_CHECK_QUORUM: u32 = 0x1;
+pub const RG_GATE_PRE_VOTE: u32 = 0x2;
+pub const RG_FOLLOW_MSG_VOTE: u32 = 0x4;
+pub const RG_FOLLOW_MSG_PREVOTE: u32 = 0x8;
+pub const RG_FOLLOW_MSG_TOUCH: u32 = 0x10;
+pub const RG_GATE_FORCE: u32 = 0x1;
+pub const RG_GATE_NONE: u32 = 0;
+pub const RG_GATE_PASS: u32 = 1;
+pub const RG_GATE_IGNORED: u32 = 2;
+pub const RG_GATE_STALE_LEADER: u32 = 3;
+pub const RG_GATE_PREVOTE_LOW: u32 = 4;
+pub const RG_GATE_VOTE_GRANT: u32 = 5;
+pub const RG_GATE_VOTE_REJECT: u32 = 6;
+pub const RG_GATE_EV_HARD_STATE: u32 = 0x1;
+pub const RG_GATE_EV_BECAME_FOLLOWER: u32 = 0x2;
+pub const RG_GATE_EV_LEADER_CHANGED: u32 = 0x4;
+pub const RG_GATE_EV_CONF_CHECK: u32 = 0x8;
 pub const RG_SEND_APPEND: u32 = 1;
 pub const RG_SEND_SNAPSHOT: u32 = 2;
 pub const RG_SEND_HOST: u32 = 3;
@@ -328,6 +345,45 @@ pub struct RgFollowOut {
 }
 
 #[repr(C)]
+pub struct RgFollowGateConfig {
+    pub election_tick: u32,
+    pub min_timeout: u32,
+    pub max_timeout: u32,
+    pub flags: u32,
+    pub seed: u64,
+}
+
+#[repr(C)]
+pub struct RgFollowSoft {
+    pub group: u64,
+    pub term: u64,
+    pub vote: u64,
+    pub leader_id: u64,
+    pub priority: i64,
+    pub election_elapsed: u32,
+    pub randomized_timeout: u32,
+    pub role: u8,
+    pub promotable: u8,
+    pub reserved: [u8; 6],
+}
+
+#[repr(C)]
+pub struct RgFollowHdr {
+    pub term: u64,
+    pub from: u64,
+    pub priority: i64,
+    pub flags: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+pub struct RgFollowGateResp {
+    pub term: u64,
+    pub gate: u32,
+    pub events: u32,
+}
+
+#[repr(C)]
 pub struct RgAppendResponse {
     pub from: u64,
     pub term: u64,
@@ -556,6 +612,13 @@ extern "C" {
     pub fn rg_follow_read(h: *mut RgEngine, host_groups: *const u64, n: u64, host_out: *mut RgFollowState) -> i32;
     pub fn rg_follow_step(h: *mut RgEngine, host_msgs: *const RgFollowMsg, n: u64, host_ext: *const RgFollowEntRun, n_ext: u64, host_resp: *mut RgFollowResp) -> i32;
     pub fn rg_follow_step_device(h: *mut RgEngine, dev_msgs: *const RgFollowMsgs, dev_out: *const RgFollowOut) -> i32;
+    pub fn rg_follow_gate_enable(h: *mut RgEngine, cfg: *const RgFollowGateConfig) -> i32;
+    pub fn rg_follow_soft_write(h: *mut RgEngine, host: *const RgFollowSoft, n: u64) -> i32;
+    pub fn rg_follow_soft_read(h: *mut RgEngine, host_groups: *const u64, n: u64, host_out: *mut RgFollowSoft) -> i32;
+    pub fn rg_follow_step_gated(h: *mut RgEngine, host_msgs: *const RgFollowMsg, host_hdr: *const RgFollowHdr, n: u64, host_ext: *const RgFollowEntRun, n_ext: u64, host_resp: *mut RgFollowResp, host_gate: *mut RgFollowGateResp) -> i32;
+    pub fn rg_follow_step_gated_device(h: *mut RgEngine, dev_msgs: *const RgFollowMsgs, dev_term: *const u64, dev_from: *const u64, dev_out: *const RgFollowOut, dev_gate: *mut u8, dev_events: *mut u8, dev_resp_term: *mut u64) -> i32;
+    pub fn rg_follow_clock(h: *mut RgEngine, dev_hup: *mut u64, cap: u64, host_n: *mut u64) -> i32;
+    pub fn rg_follow_clock_counts(h: *const RgEngine) -> *const u64;
     pub fn rg_set_peers(h: *mut RgEngine, group: u64, peer_ids: *const u64, n: u32, term: u64) -> i32;
     pub fn rg_step(h: *mut RgEngine, group: u64, m: *const RgAppendResponse) -> i32;
     pub fn rg_step_heartbeat_response(h: *mut RgEngine, group: u64, from: u64, term: u64, commit: u64, ins_full: u8) -> i32;

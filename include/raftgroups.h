@@ -41,7 +41,7 @@ extern "C" {
  * new members keep the old meaning), so a caller is compiled against the header of the library it loads. RG_ABI_VERSION is bumped
  * whenever a struct layout, an enum value or a signature changes; rg_abi_version() returns what the library was built with --
  * compare the two at start-up (raftgroups.hpp and the Python / Rust bindings do). */
-#define RG_ABI_VERSION 9u
+#define RG_ABI_VERSION 10u
 
 /* ---- status codes; the negative values mirror src/errors.rs:6-50 where one applies ----
  * Every entry point that returns int returns one of these and leaves the text in rg_last_error() (per thread). Nothing unwinds
@@ -644,8 +644,9 @@ int rg_read_pending_counts(rg_engine *h, uint8_t *host_counts);
  *     RG_TERM_RUNS older terms since its snapshot never raises it. The host handles the message with its own RaftLog and
  *     re-loads the group with rg_follow_write.
  *   FAULT and HOST answer {index = m.index, commit = committed}.
- * The term gate of Raft::step (src/raft.rs:1282-1411), become_follower, election_elapsed, leader_id, snapshots, `persisted` and
- * turning a response record into a Message stay on the host.
+ * Snapshots, `persisted` and turning a response record into a Message stay on the host; so do the term gate of Raft::step
+ * (src/raft.rs:1282-1411), become_follower, election_elapsed and leader_id unless rg_follow_gate_enable (next section) puts
+ * them on the device, where rg_follow_step_gated / rg_follow_step_gated_device run the gate in front of these steps.
  * Every call before rg_follow_enable returns RG_ERR_STATE, so does a second enable. rg_checkpoint / rg_restore include the
  * arena, rg_destroy frees it, rg_device_info.engine_bytes grows by its size. */
 #define RG_FOLLOW_RUNS 9 /* RG_TERM_RUNS older runs + the tail */
@@ -709,6 +710,109 @@ typedef struct {
     uint64_t *index, *commit, *conflict, *reject_hint, *log_term;
 } rg_follow_out;
 int rg_follow_step_device(rg_engine *h, const rg_follow_msgs *dev_msgs, const rg_follow_out *dev_out);
+
+/* ---- The follower's term gate, vote step and election clock (the gate of Raft::step, src/raft.rs:1282-1411; the vote step,
+ *      :1418-1461; reset / become_follower, :942-971, :1082-1087; step_candidate / step_follower, :2215-2229, :2271-2285;
+ *      tick_election, :1024-1047; maybe_commit_by_vote, :2126-2164; RaftLog::is_up_to_date / maybe_commit / commit_info,
+ *      src/raft_log.rs:412, :487, :637) ----
+ * Optional, on top of the follower arena: per followed group the "soft" state of a non-leader -- term, leader_id, vote,
+ * priority, role, promotable, election_elapsed and randomized_election_timeout. With it the arena answers every integer
+ * question Raft::step asks of a non-leader; the host keeps bytes (entries, snapshots, contexts) and campaigning (hup, campaign,
+ * vote responses, poll), MsgTimeoutNow, handle_snapshot / restore.
+ *   HOT cells: term u64, lead u64, clock u32 (election_elapsed in bits 0..14, promotable in bit 15, the randomized timeout in
+ *   bits 16..31). COLD cells: vote u64, priority i64, role u8. 37 bytes per group of the stride. A steady append (equal term,
+ *   unchanged leader) reads the three hot cells and writes the clock cell -- if election_elapsed was not 0 already.
+ *   Invariant kept by every call: role != Follower implies leader_id == 0 (become_candidate / become_pre_candidate clear it);
+ *   it is what lets the steady append skip the role cell.
+ * rg_follow_step / rg_follow_step_device / rg_follow_write do not touch these cells.
+ * Every call of this section before rg_follow_gate_enable returns RG_ERR_STATE, so does a second enable. rg_checkpoint /
+ * rg_restore carry the cells, rg_destroy frees them, rg_device_info.engine_bytes grows by their size. */
+#define RG_GATE_CHECK_QUORUM 0x1u /* Config::check_quorum */
+#define RG_GATE_PRE_VOTE 0x2u     /* Config::pre_vote */
+typedef struct {
+    uint32_t election_tick;            /* Config::election_tick, 1..16383 */
+    uint32_t min_timeout, max_timeout; /* min/max_election_tick; 0,0 = [election_tick, 2*election_tick); else election_tick <= min < max <= 32767 */
+    uint32_t flags;                    /* RG_GATE_CHECK_QUORUM | RG_GATE_PRE_VOTE */
+    uint64_t seed;                     /* of the timeout draws */
+} rg_follow_gate_config;
+/* Once, after rg_follow_enable. Every group starts as a Follower at term 0 that is not promotable, with a drawn timeout. */
+int rg_follow_gate_enable(rg_engine *h, const rg_follow_gate_config *cfg);
+/* The timeout draw (the reference draws from thread_rng, src/raft.rs:2744-2756: only the range is semantics) is
+ * rg_follow_draw(seed, group, term, previous_timeout, min, max) of csrc/rg_follow.h, a splitmix64 chain; `term` is the term
+ * AFTER the reset. Chaining the previous timeout gives a fresh draw on every reset, also within one term. */
+typedef struct {
+    uint64_t group, term, vote, leader_id;
+    int64_t priority;
+    uint32_t election_elapsed, randomized_timeout; /* randomized_timeout 0 = draw one (previous_timeout = the cell's) */
+    uint8_t role, promotable, reserved[6];         /* role: 0 Follower, 1 PreCandidate, 2 Candidate */
+} rg_follow_soft;
+/* Control path; synchronises. RG_ERR_INVALID_ARG, and nothing written, for a group at or beyond n_follow, a role above 2, a
+ * role other than Follower with a leader_id, a timeout outside [min, max) unless it is 0, election_elapsed above 32767,
+ * promotable above 1, or two records of one group in the call. */
+int rg_follow_soft_write(rg_engine *h, const rg_follow_soft *host, uint64_t n);
+int rg_follow_soft_read(rg_engine *h, const uint64_t *host_groups, uint64_t n, rg_follow_soft *host_out);
+/* Message kinds of the gated step, beside RG_FOLLOW_MSG_APPEND / _HEARTBEAT, in rg_follow_msg.flags (exactly one):
+ *   VOTE / PREVOTE  MsgRequestVote / MsgRequestPreVote: index / log_term = the candidate's last entry, commit = Message.commit,
+ *                   ent_term = Message.commit_term, n_entries = 0 and no ext.
+ *   TOUCH           a MsgSnapshot the host steps itself: through the gate, then election_elapsed = 0, leader_id = from. */
+#define RG_FOLLOW_MSG_VOTE 0x4u
+#define RG_FOLLOW_MSG_PREVOTE 0x8u
+#define RG_FOLLOW_MSG_TOUCH 0x10u
+#define RG_GATE_FORCE 0x1u /* rg_follow_hdr.flags: Message.context == CAMPAIGN_TRANSFER */
+typedef struct {
+    uint64_t term, from; /* Message.term (never 0: a local message), Message.from (never 0) */
+    int64_t priority;    /* Message.priority (vote kinds) */
+    uint32_t flags, reserved;
+} rg_follow_hdr;
+typedef struct {
+    uint64_t term; /* the term the response carries */
+    uint32_t gate, events;
+} rg_follow_gate_resp;
+/* gate: what became of the record.
+ *   PASS          the step ran (APPEND / HEARTBEAT: rg_follow_resp as in rg_follow_step; TOUCH: status 0). term = the group's.
+ *                 Where the step answers RG_FOLLOW_FAULT or RG_FOLLOW_HOST NOTHING of the group changed, the soft cells
+ *                 included (the gate's become_follower is undone): gate PASS, events 0, term = the unchanged term.
+ *   IGNORED       nothing changed, nothing is sent: a (pre-)vote request inside the lease (m.term > term, CHECK_QUORUM,
+ *                 leader_id != 0, election_elapsed < election_tick, no FORCE), or m.term < term and no answer is due.
+ *   STALE_LEADER  m.term < term, APPEND / HEARTBEAT under CHECK_QUORUM or PRE_VOTE: send the empty MsgAppendResponse.
+ *   PREVOTE_LOW   m.term < term, PREVOTE: send the reject, term = the group's.
+ *   VOTE_GRANT    term = m.term. A real vote also did election_elapsed = 0, vote = from. rg_follow_resp.commit = committed.
+ *   VOTE_REJECT   term = the group's; rg_follow_resp.commit / .log_term = RaftLog::commit_info() taken BEFORE
+ *                 maybe_commit_by_vote, which then ran (RaftLog::maybe_commit(m.commit, m.commit_term)).
+ * m.term > term: everything but a pre-vote runs become_follower(m.term, from for APPEND / HEARTBEAT / TOUCH, 0 for VOTE) =
+ * reset: term and vote if the term differs, leader_id, a new timeout draw, election_elapsed = 0, role = Follower. Equal terms:
+ * a PreCandidate or Candidate that gets APPEND / HEARTBEAT / TOUCH runs become_follower(m.term, from) first.
+ * RG_FOLLOW_HOST (rg_follow_resp.status; nothing changed) also where term(committed) of commit_info or term(m.commit) of
+ * maybe_commit lies in the dropped gap and the interval rule does not settle it. */
+#define RG_GATE_NONE 0u
+#define RG_GATE_PASS 1u
+#define RG_GATE_IGNORED 2u
+#define RG_GATE_STALE_LEADER 3u
+#define RG_GATE_PREVOTE_LOW 4u
+#define RG_GATE_VOTE_GRANT 5u
+#define RG_GATE_VOTE_REJECT 6u
+#define RG_GATE_EV_HARD_STATE 0x1u      /* term, vote or commit changed: persist before sending the response */
+#define RG_GATE_EV_BECAME_FOLLOWER 0x2u /* the role was a candidate's: the host drops its vote tally */
+#define RG_GATE_EV_LEADER_CHANGED 0x4u  /* leader_id changed */
+#define RG_GATE_EV_CONF_CHECK 0x8u      /* maybe_commit_by_vote advanced the commit of a (pre-)candidate: the host counts the pending
+                                           conf entries of (old commit, new commit] and steps down with rg_follow_soft_write */
+/* Sparse, all five kinds: as rg_follow_step, host_hdr[i] beside host_msgs[i]; host_gate[i] answers too. RG_ERR_INVALID_ARG,
+ * and nothing applied, also for a term or a from of 0 and for a vote kind with entries. Synchronises. */
+int rg_follow_step_gated(rg_engine *h, const rg_follow_msg *host_msgs, const rg_follow_hdr *host_hdr, uint64_t n,
+                         const rg_follow_ent_run *host_ext, uint64_t n_ext, rg_follow_resp *host_resp, rg_follow_gate_resp *host_gate);
+/* Dense, APPEND / HEARTBEAT / TOUCH only (a vote kind, a term or a from of 0 answer status RG_FOLLOW_FAULT, gate 0): as
+ * rg_follow_step_device, with the columns dev_term / dev_from of Message.term / Message.from. dev_gate and dev_events are
+ * written for every group (0 = no message), dev_resp_term where there was a message. Asynchronous. */
+int rg_follow_step_gated_device(rg_engine *h, const rg_follow_msgs *dev_msgs, const uint64_t *dev_term, const uint64_t *dev_from,
+                                const rg_follow_out *dev_out, uint8_t *dev_gate, uint8_t *dev_events, uint64_t *dev_resp_term);
+/* One Raft::tick of every followed group: election_elapsed += 1 (it saturates at 32767); a promotable group whose
+ * election_elapsed has reached its timeout is DUE: it is appended to dev_hup[cap] (device memory, order unspecified) and its
+ * election_elapsed becomes 0 -- the host runs hup() for it and writes role, term and vote back with rg_follow_soft_write. A due
+ * group that did not fit is NOT reset: it is due again on the next call. *host_n = the number appended = min(cap, due);
+ * host_n == NULL keeps the call asynchronous: the counts are in the two device words of rg_follow_clock_counts. */
+int rg_follow_clock(rg_engine *h, uint64_t *dev_hup, uint64_t cap, uint64_t *host_n);
+/* device u64 [2] the last rg_follow_clock wrote: [0] groups appended, [1] groups due; NULL before rg_follow_gate_enable */
+const uint64_t *rg_follow_clock_counts(const rg_engine *h);
 
 /* ---- message-at-a-time host mirror of RawNode::step for MsgAppendResponse
  *      (src/raw_node.rs:402-411 -> src/raft.rs:1280-1411 term gate -> :2096-2098) ---- */

@@ -121,6 +121,12 @@ struct RgFollowEngine {
     std::vector<char> stage;             // host staging of one sparse batch / one read
     std::vector<u32> order;              // ... its records' positions, sorted by group
     std::vector<rg_follow_state> states; // ... of one rg_follow_write
+    // the term gate, the vote step and the election clock (rg_follow_gate_enable): the soft columns of RgSoftCols, [stride] each,
+    // then the two count words of rg_follow_clock (which no checkpoint carries); soft_arena == nullptr = off
+    RgSoftCols soft;
+    char *soft_arena, *soft_ckpt;
+    size_t soft_bytes;               // of the columns
+    unsigned long long *clock_counts; // device u64 [2]: groups appended, groups due
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // rg_follow.h -- the follower half: the per-group arithmetic of a MsgAppend / MsgHeartbeat step (include/raftgroups.h: "The
-// follower half").
+// follower half") and, in the second part of this file, of what stands in front of it and beside it in a non-leader's
+// Raft::step: the term gate, the vote step and the election clock ("The follower's term gate, vote step and election clock").
 //
 // The engine's restatement of Raft::handle_append_entries (src/raft.rs:2389-2448, from :2394 on) and Raft::handle_heartbeat
 // (:2452-2464) over RaftLog::term (src/raft_log.rs:122-140), match_term (:238), find_conflict (:182-198), find_conflict_by_term
@@ -19,7 +20,7 @@
 //
 // Host/device-clean: the kernels (rg_kernels_follow.h) include it behind rg_common.h; a host program includes it ALONE and
 // compiles it with any C++17 compiler (tests/host_check/follow_twin.cpp is checked that way against tests/follower_model.py,
-// sanitizers included) -- nothing below needs the HIP headers.
+// tests/host_check/gate_twin.cpp against tests/gate_model.py, sanitizers included) -- nothing below needs the HIP headers.
 #pragma once
 #include <stdint.h>
 
@@ -337,4 +338,247 @@ RG_D rg_follow_state rg_follow_load_state(const RgFollowCols &c, u64 g) {
         s.run_term[k] = old ? c.run_term[(u64)k * c.stride + g] : (tail && k == n_old) ? c.tail_term[g] : 0;
     }
     return s;
+}
+
+// ---- the term gate, the vote step and the election clock (include/raftgroups.h: "The follower's term gate ...") ----
+// Restated from Raft::step (src/raft.rs:1282-1411 the gate, :1418-1461 the vote step), reset / become_follower (:942-971,
+// :1082-1087), step_candidate / step_follower (:2215-2229, :2271-2285), tick_election (:1024-1047), maybe_commit_by_vote
+// (:2126-2164), RaftLog::is_up_to_date / maybe_commit / commit_info (src/raft_log.rs:412, :487, :637).
+struct RgGateCfg {
+    u32 election_tick, min_timeout, max_timeout, flags;
+    u64 seed;
+};
+// The soft columns, F = stride groups each. HOT: term, lead, clock. COLD: vote, priority, role.
+struct RgSoftCols {
+    u64 *term, *lead;
+    u32 *clock; // election_elapsed | promotable << 15 | randomized_election_timeout << 16
+    u64 *vote;
+    int64_t *priority;
+    u8 *role;
+    RgGateCfg cfg;
+};
+#define RG_CLOCK_ELAPSED_MAX 0x7fffu
+RG_D u32 rg_clock_elapsed(u32 c) { return c & RG_CLOCK_ELAPSED_MAX; }
+RG_D u32 rg_clock_promotable(u32 c) { return (c >> 15) & 1u; }
+RG_D u32 rg_clock_timeout(u32 c) { return c >> 16; }
+RG_D u32 rg_clock_pack(u32 elapsed, u32 promotable, u32 timeout) { return elapsed | (promotable << 15) | (timeout << 16); }
+
+RG_D u64 rg_follow_mix(u64 z) { // splitmix64's step
+    z += 0x9e3779b97f4a7c15ULL;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+    return z ^ (z >> 31);
+}
+// reset_randomized_election_timeout (raft.rs:2744-2756): a value of [min, max), from the seed, the group, the term after the
+// reset and the timeout it replaces
+RG_D u32 rg_follow_draw(u64 seed, u64 group, u64 term, u32 prev, u32 min, u32 max) {
+    const u64 x = rg_follow_mix(rg_follow_mix(rg_follow_mix(seed ^ group) ^ term) ^ prev);
+    return min + (u32)(x >> 32) % (max - min);
+}
+
+// One group's soft state while a lane works on it: the hot cells by value, the cold ones loaded on first use and written back
+// only where a record changed them (`have`: 1 vote loaded, 2 role loaded, 4 vote to be stored, 8 role to be stored).
+struct RgSoftView {
+    u64 term, lead, vote;
+    u32 clock, role, have;
+    const u64 *pvote;
+    const int64_t *ppriority;
+    const u8 *prole;
+};
+RG_D RgSoftView rg_soft_open(const RgSoftCols &c, u64 g) {
+    RgSoftView s;
+    s.term = c.term[g];
+    s.lead = c.lead[g];
+    s.clock = c.clock[g];
+    s.vote = 0;
+    s.role = 0;
+    s.have = 0;
+    s.pvote = c.vote + g;
+    s.ppriority = c.priority + g;
+    s.prole = c.role + g;
+    return s;
+}
+RG_D void rg_soft_close(const RgSoftCols &c, u64 g, const RgSoftView &s, const RgSoftView &o) {
+    if (s.term != o.term) c.term[g] = s.term;
+    if (s.lead != o.lead) c.lead[g] = s.lead;
+    if (s.clock != o.clock) c.clock[g] = s.clock;
+    if (s.have & 4u) c.vote[g] = s.vote;
+    if (s.have & 8u) c.role[g] = (u8)s.role;
+}
+RG_D u64 rg_soft_vote(RgSoftView &s) {
+    if (!(s.have & 1u)) {
+        s.vote = *s.pvote;
+        s.have |= 1u;
+    }
+    return s.vote;
+}
+RG_D u32 rg_soft_role(RgSoftView &s) {
+    if (!(s.have & 2u)) {
+        s.role = *s.prole;
+        s.have |= 2u;
+    }
+    return s.role;
+}
+RG_D void rg_soft_set_vote(RgSoftView &s, u64 vote) {
+    s.vote = vote;
+    s.have |= 5u;
+}
+RG_D void rg_soft_set_elapsed(RgSoftView &s, u32 elapsed) { s.clock = (s.clock & ~RG_CLOCK_ELAPSED_MAX) | elapsed; }
+
+// become_follower(term, lead) (raft.rs:1082-1087) = reset(term) (:942-971) as far as a non-leader has the state
+RG_D void rg_gate_become_follower(const RgGateCfg &cfg, u64 g, RgSoftView &s, u64 term, u64 lead, u32 &events) {
+    if (s.term != term) {
+        s.term = term;
+        rg_soft_set_vote(s, 0);
+    }
+    s.lead = lead;
+    const u32 timeout = rg_follow_draw(cfg.seed, g, s.term, rg_clock_timeout(s.clock), cfg.min_timeout, cfg.max_timeout);
+    s.clock = rg_clock_pack(0, rg_clock_promotable(s.clock), timeout);
+    if (rg_soft_role(s) != 0) {
+        events |= RG_GATE_EV_BECAME_FOLLOWER;
+        s.role = 0;
+        s.have |= 8u;
+    }
+}
+
+// A well-formed gated record? (what the dense kernel answers FAULT to and the sparse call refuses on the host)
+RG_FOLLOW_HD bool rg_gate_well_formed(u32 kind, u64 term, u64 from, u32 n_entries, u32 n_ext, bool votes) {
+    const u32 steps = RG_FOLLOW_MSG_APPEND | RG_FOLLOW_MSG_HEARTBEAT | RG_FOLLOW_MSG_TOUCH, vote_kinds = RG_FOLLOW_MSG_VOTE | RG_FOLLOW_MSG_PREVOTE;
+    if (kind == 0 || (kind & (kind - 1)) != 0 || term == 0 || from == 0) return false;
+    if (kind & steps) return true;
+    return votes && (kind & vote_kinds) != 0 && n_entries == 0 && n_ext == 0;
+}
+
+RG_D rg_follow_gate_resp rg_gate_answer(u64 term, u32 gate, u32 events) {
+    rg_follow_gate_resp a;
+    a.term = term;
+    a.gate = gate;
+    a.events = events;
+    return a;
+}
+
+// One well-formed record through the gate and its step. `r` is the step's answer (status 0 where no log step ran). Nothing
+// of `s` or `v` changes where the answer is IGNORED / STALE_LEADER / PREVOTE_LOW or the status is FAULT / HOST.
+RG_D rg_follow_gate_resp rg_gate_step(const RgGateCfg &cfg, u64 g, RgSoftView &s, RgFollowView &v, const RgFollowRec &m, u64 m_term, u64 from,
+                                      int64_t m_priority, u32 hdr_flags, rg_follow_resp &r) {
+    const u32 kind = m.flags;
+    const bool vote_kind = (kind & (RG_FOLLOW_MSG_VOTE | RG_FOLLOW_MSG_PREVOTE)) != 0;
+    const RgSoftView s0 = s;
+    const u64 committed0 = v.committed;
+    u32 events = 0;
+    r = rg_follow_answer(RG_FOLLOW_NONE, m.index, v.committed);
+    if (m_term > s.term) {
+        if (vote_kind) {
+            const bool in_lease = (cfg.flags & RG_GATE_CHECK_QUORUM) && s.lead != 0 && rg_clock_elapsed(s.clock) < cfg.election_tick;
+            if (!(hdr_flags & RG_GATE_FORCE) && in_lease) return rg_gate_answer(s.term, RG_GATE_IGNORED, 0);
+        }
+        if (kind != RG_FOLLOW_MSG_PREVOTE) rg_gate_become_follower(cfg, g, s, m_term, kind == RG_FOLLOW_MSG_VOTE ? 0 : from, events);
+    } else if (m_term < s.term) {
+        if ((cfg.flags & (RG_GATE_CHECK_QUORUM | RG_GATE_PRE_VOTE)) && (kind & (RG_FOLLOW_MSG_APPEND | RG_FOLLOW_MSG_HEARTBEAT)))
+            return rg_gate_answer(s.term, RG_GATE_STALE_LEADER, 0);
+        return rg_gate_answer(s.term, kind == RG_FOLLOW_MSG_PREVOTE ? RG_GATE_PREVOTE_LOW : RG_GATE_IGNORED, 0);
+    }
+    u32 gate = RG_GATE_PASS;
+    u64 resp_term = s.term;
+    bool undone = false;
+    if (vote_kind) {
+        const bool can_vote = rg_soft_vote(s) == from || (s.vote == 0 && s.lead == 0) || (kind == RG_FOLLOW_MSG_PREVOTE && m_term > s.term);
+        bool grant = can_vote;
+        if (grant) { // is_up_to_date(m.index, m.log_term) (raft_log.rs:412); the last entry is the tail's or the dummy entry
+            const RgFollowSeg lt = rg_follow_seg(v, v.last);
+            if (lt.lo != lt.hi) undone = true;
+            else grant = m.log_term > lt.lo || (m.log_term == lt.lo && m.index >= v.last);
+        }
+        if (grant && !undone) grant = m.index > v.last || *s.ppriority <= m_priority;
+        if (undone) {
+        } else if (grant) {
+            gate = RG_GATE_VOTE_GRANT;
+            resp_term = m_term;
+            if (kind == RG_FOLLOW_MSG_VOTE) { // only real votes are recorded
+                rg_soft_set_elapsed(s, 0);
+                if (s.vote != from) events |= RG_GATE_EV_HARD_STATE;
+                rg_soft_set_vote(s, from);
+            }
+        } else {
+            gate = RG_GATE_VOTE_REJECT;
+            const RgFollowSeg ct = rg_follow_seg(v, v.committed); // commit_info (raft_log.rs:637)
+            if (ct.lo != ct.hi) undone = true;
+            else {
+                r.log_term = ct.lo;
+                // maybe_commit_by_vote (raft.rs:2126-2164) -> RaftLog::maybe_commit(m.commit, m.commit_term)
+                if (m.commit != 0 && m.ent_term != 0 && m.commit > v.committed) {
+                    const RgFollowSeg at = rg_follow_seg(v, m.commit);
+                    if (at.lo != at.hi && m.ent_term >= at.lo && m.ent_term <= at.hi) undone = true;
+                    else if (at.lo == at.hi && at.lo == m.ent_term) {
+                        v.committed = m.commit; // (term(m.commit) != 0: m.commit <= last_index)
+                        if (rg_soft_role(s) != 0) events |= RG_GATE_EV_CONF_CHECK;
+                    }
+                }
+            }
+        }
+    } else {
+        // step_candidate (raft.rs:2215-2229): role != Follower implies lead == 0, so a group with a leader skips the role cell
+        if (s.lead == 0 && rg_soft_role(s) != 0) rg_gate_become_follower(cfg, g, s, m_term, from, events);
+        rg_soft_set_elapsed(s, 0); // step_follower (:2271-2285)
+        s.lead = from;
+        if (kind != RG_FOLLOW_MSG_TOUCH) {
+            r = rg_follow_apply(v, m);
+            undone = r.status == RG_FOLLOW_FAULT || r.status == RG_FOLLOW_HOST;
+        }
+    }
+    if (undone) {
+        s = s0;
+        v.committed = committed0;
+        if (r.status != RG_FOLLOW_FAULT) r = rg_follow_answer(RG_FOLLOW_HOST, m.index, v.committed);
+        return rg_gate_answer(s.term, RG_GATE_PASS, 0);
+    }
+    if (s.term != s0.term || v.committed != committed0) events |= RG_GATE_EV_HARD_STATE;
+    if (s.lead != s0.lead) events |= RG_GATE_EV_LEADER_CHANGED;
+    return rg_gate_answer(resp_term, gate, events);
+}
+
+// Raft::tick of a non-leader (raft.rs:1024-1047) on the clock cell: the new cell if the group does not fire, and whether it is
+// due. A due group's election_elapsed becomes 0 only if its hup is delivered (the caller decides).
+RG_D u32 rg_clock_tick(u32 c, bool &due) {
+    u32 e = rg_clock_elapsed(c);
+    if (e < RG_CLOCK_ELAPSED_MAX) e++;
+    due = e >= rg_clock_timeout(c) && rg_clock_promotable(c);
+    return (c & ~RG_CLOCK_ELAPSED_MAX) | e;
+}
+
+// ---- rg_follow_soft_write / rg_follow_soft_read ----
+// 0 = acceptable, else which rule it breaks
+RG_FOLLOW_HD int rg_follow_soft_check(const rg_follow_soft &w, u32 min_timeout, u32 max_timeout) {
+    if (w.role > 2) return 1;
+    if (w.role != 0 && w.leader_id != 0) return 2;
+    if (w.randomized_timeout != 0 && (w.randomized_timeout < min_timeout || w.randomized_timeout >= max_timeout)) return 3;
+    if (w.election_elapsed > RG_CLOCK_ELAPSED_MAX) return 4;
+    if (w.promotable > 1) return 5;
+    return 0;
+}
+RG_D void rg_follow_store_soft(const RgSoftCols &c, const rg_follow_soft &w) {
+    const u64 g = w.group;
+    u32 timeout = w.randomized_timeout;
+    if (timeout == 0) timeout = rg_follow_draw(c.cfg.seed, g, w.term, rg_clock_timeout(c.clock[g]), c.cfg.min_timeout, c.cfg.max_timeout);
+    c.term[g] = w.term;
+    c.lead[g] = w.leader_id;
+    c.clock[g] = rg_clock_pack(w.election_elapsed, w.promotable, timeout);
+    c.vote[g] = w.vote;
+    c.priority[g] = w.priority;
+    c.role[g] = w.role;
+}
+RG_D rg_follow_soft rg_follow_load_soft(const RgSoftCols &c, u64 g) {
+    rg_follow_soft w;
+    const u32 k = c.clock[g];
+    w.group = g;
+    w.term = c.term[g];
+    w.vote = c.vote[g];
+    w.leader_id = c.lead[g];
+    w.priority = c.priority[g];
+    w.election_elapsed = rg_clock_elapsed(k);
+    w.randomized_timeout = rg_clock_timeout(k);
+    w.role = c.role[g];
+    w.promotable = (u8)rg_clock_promotable(k);
+    for (int i = 0; i < 6; i++) w.reserved[i] = 0;
+    return w;
 }

@@ -206,7 +206,7 @@ class PublishStats(C.Structure):
                 ("events_on_tick_packets", C.c_uint64)]
 
 
-ABI_VERSION = 9  # RG_ABI_VERSION of include/raftgroups.h these ctypes layouts mirror (tests/test_abi.py compares)
+ABI_VERSION = 10  # RG_ABI_VERSION of include/raftgroups.h these ctypes layouts mirror (tests/test_abi.py compares)
 class CommInfo(C.Structure):
     _fields_ = [("rank", C.c_uint32), ("world", C.c_uint32), ("transport", C.c_uint32), ("in_process", C.c_uint32),
                 ("rccl_ranks", C.c_uint32), ("rccl_rank", C.c_uint32)]
@@ -248,6 +248,24 @@ FOLLOW_RESP_DTYPE = np.dtype([("index", "<u8"), ("commit", "<u8"), ("conflict", 
 assert (FOLLOW_STATE_DTYPE.itemsize, FOLLOW_ENT_RUN_DTYPE.itemsize, FOLLOW_MSG_DTYPE.itemsize, FOLLOW_RESP_DTYPE.itemsize) == (192, 16, 56, 48)
 FOLLOW_MSG_APPEND, FOLLOW_MSG_HEARTBEAT = 1, 2
 FOLLOW_NONE, FOLLOW_ACCEPT, FOLLOW_REJECT, FOLLOW_STALE, FOLLOW_HEARTBEAT, FOLLOW_FAULT, FOLLOW_HOST = 0, 1, 2, 3, 4, 5, 6
+# ... its term gate, vote step and election clock (rg_follow_gate_enable ...)
+FOLLOW_SOFT_DTYPE = np.dtype([("group", "<u8"), ("term", "<u8"), ("vote", "<u8"), ("leader_id", "<u8"), ("priority", "<i8"),
+                              ("election_elapsed", "<u4"), ("randomized_timeout", "<u4"), ("role", "u1"), ("promotable", "u1"),
+                              ("reserved", "u1", (6,))])                                             # rg_follow_soft
+FOLLOW_HDR_DTYPE = np.dtype([("term", "<u8"), ("from", "<u8"), ("priority", "<i8"), ("flags", "<u4"), ("reserved", "<u4")])  # rg_follow_hdr
+FOLLOW_GATE_RESP_DTYPE = np.dtype([("term", "<u8"), ("gate", "<u4"), ("events", "<u4")])            # rg_follow_gate_resp
+assert (FOLLOW_SOFT_DTYPE.itemsize, FOLLOW_HDR_DTYPE.itemsize, FOLLOW_GATE_RESP_DTYPE.itemsize) == (56, 32, 16)
+FOLLOW_MSG_VOTE, FOLLOW_MSG_PREVOTE, FOLLOW_MSG_TOUCH = 4, 8, 16
+GATE_CHECK_QUORUM, GATE_PRE_VOTE = 1, 2
+GATE_FORCE = 1
+GATE_NONE, GATE_PASS, GATE_IGNORED, GATE_STALE_LEADER, GATE_PREVOTE_LOW, GATE_VOTE_GRANT, GATE_VOTE_REJECT = 0, 1, 2, 3, 4, 5, 6
+GATE_EV_HARD_STATE, GATE_EV_BECAME_FOLLOWER, GATE_EV_LEADER_CHANGED, GATE_EV_CONF_CHECK = 1, 2, 4, 8
+ROLE_FOLLOWER, ROLE_PRE_CANDIDATE, ROLE_CANDIDATE = 0, 1, 2
+
+
+class FollowGateConfig(C.Structure):  # rg_follow_gate_config
+    _fields_ = [("election_tick", C.c_uint32), ("min_timeout", C.c_uint32), ("max_timeout", C.c_uint32), ("flags", C.c_uint32),
+                ("seed", C.c_uint64)]
 
 
 class FollowMsgs(C.Structure):  # rg_follow_msgs: device pointers
@@ -338,6 +356,13 @@ SYMBOLS = {
     "rg_follow_read": (_i, [_vp, _vp, _u64, _vp]),
     "rg_follow_step": (_i, [_vp, _vp, _u64, _vp, _u64, _vp]),
     "rg_follow_step_device": (_i, [_vp, C.POINTER(FollowMsgs), C.POINTER(FollowOut)]),
+    "rg_follow_gate_enable": (_i, [_vp, C.POINTER(FollowGateConfig)]),
+    "rg_follow_soft_write": (_i, [_vp, _vp, _u64]),
+    "rg_follow_soft_read": (_i, [_vp, _vp, _u64, _vp]),
+    "rg_follow_step_gated": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "rg_follow_step_gated_device": (_i, [_vp, C.POINTER(FollowMsgs), _vp, _vp, C.POINTER(FollowOut), _vp, _vp, _vp]),
+    "rg_follow_clock": (_i, [_vp, _vp, _u64, _vp]),
+    "rg_follow_clock_counts": (_vp, [_vp]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -970,6 +995,61 @@ class Engine:
                        int(msgs.get("n_ext", 0)))
         o = FollowOut(*[p(out.get(k)) for k in ("status", "index", "commit", "conflict", "reject_hint", "log_term")])
         self._check(self.L.rg_follow_step_device(self.h, C.byref(m), C.byref(o)))
+
+    # ---- the follower's term gate, vote step and election clock ------------------------------------
+    def follow_gate_enable(self, election_tick, min_timeout=0, max_timeout=0, flags=0, seed=0):
+        """rg_follow_gate_enable: the soft cells of every followed group. Once, after follow_enable."""
+        cfg = FollowGateConfig(election_tick, min_timeout, max_timeout, flags, seed)
+        self._check(self.L.rg_follow_gate_enable(self.h, C.byref(cfg)))
+
+    def follow_soft_write(self, soft):
+        """Load soft states: a FOLLOW_SOFT_DTYPE array (distinct groups; randomized_timeout 0 = draw one)."""
+        soft = np.ascontiguousarray(soft, dtype=FOLLOW_SOFT_DTYPE)
+        self._check(self.L.rg_follow_soft_write(self.h, soft.ctypes.data, len(soft)))
+
+    def follow_soft_read(self, groups):
+        groups = np.ascontiguousarray(groups, dtype=np.uint64)
+        out = np.zeros(len(groups), dtype=FOLLOW_SOFT_DTYPE)
+        self._check(self.L.rg_follow_soft_read(self.h, groups.ctypes.data, len(groups), out.ctypes.data))
+        return out
+
+    def follow_step_gated(self, msgs, hdrs, ext=None):
+        """Sparse gated step, all five kinds: msgs (FOLLOW_MSG_DTYPE) and hdrs (FOLLOW_HDR_DTYPE), positional ->
+        (FOLLOW_RESP_DTYPE array, FOLLOW_GATE_RESP_DTYPE array)."""
+        msgs = np.ascontiguousarray(msgs, dtype=FOLLOW_MSG_DTYPE)
+        hdrs = np.ascontiguousarray(hdrs, dtype=FOLLOW_HDR_DTYPE)
+        if len(hdrs) != len(msgs):
+            raise ValueError("one header per record")
+        n_ext = 0 if ext is None else len(ext)
+        if n_ext:
+            ext = np.ascontiguousarray(ext, dtype=FOLLOW_ENT_RUN_DTYPE)
+        resp = np.zeros(len(msgs), dtype=FOLLOW_RESP_DTYPE)
+        gate = np.zeros(len(msgs), dtype=FOLLOW_GATE_RESP_DTYPE)
+        self._check(self.L.rg_follow_step_gated(self.h, msgs.ctypes.data, hdrs.ctypes.data, len(msgs), ext.ctypes.data if n_ext else None, n_ext,
+                                                resp.ctypes.data, gate.ctypes.data))
+        return resp, gate
+
+    def follow_step_gated_device(self, msgs, term, from_, out, gate, events, resp_term):
+        """Dense gated step (asynchronous): as follow_step_device, with the DEVICE columns term / from_ (u64) and the outputs
+        gate / events (u8) and resp_term (u64)."""
+        def p(x):
+            return None if x is None else int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+        m = FollowMsgs(*[p(msgs.get(k)) for k in ("flags", "index", "log_term", "commit", "ent_term", "n_entries", "ext", "ext_runs")],
+                       int(msgs.get("n_ext", 0)))
+        o = FollowOut(*[p(out.get(k)) for k in ("status", "index", "commit", "conflict", "reject_hint", "log_term")])
+        self._check(self.L.rg_follow_step_gated_device(self.h, C.byref(m), p(term), p(from_), C.byref(o), p(gate), p(events), p(resp_term)))
+
+    def follow_clock(self, hup, cap, sync=True):
+        """rg_follow_clock: one Raft::tick of every followed group; hup = DEVICE u64 [cap] (None with cap 0). sync: -> the number
+        appended; else asynchronous, the counts are the two device words at follow_clock_counts()."""
+        ptr = None if hup is None else int(hup.data_ptr()) if hasattr(hup, "data_ptr") else int(hup)
+        n = C.c_uint64(0)
+        self._check(self.L.rg_follow_clock(self.h, ptr, cap, C.byref(n) if sync else None))
+        return n.value if sync else None
+
+    def follow_clock_counts(self):
+        """Device address of u64 [2]: groups appended, groups due, of the last follow_clock."""
+        return self.L.rg_follow_clock_counts(self.h)
 
     # ---- message-at-a-time mirror of RawNode::step -----------------------------------------------
     def set_peers(self, group, peer_ids, term):
