@@ -4,30 +4,48 @@
 #include "rg_kernels_sparse.h"
 
 static RgIngest rg_ingest_args(rg_engine *h, const rg_wire_msg *rec, u64 n, const RgClear &clr) {
-    RgIngest a;
-    a.rec = rec;
-    a.n = n;
-    a.G = h->G;
-    a.stride = h->stride;
-    a.P = h->P;
-    a.mi = (u64 *)h->staged.mi;
-    a.mc = (u64 *)h->staged.mc;
-    a.mh = (u64 *)h->staged.mh;
-    a.mrs = (u64 *)h->staged.mrs;
-    a.mlt = (u64 *)h->staged.mlt;
-    a.mflags32 = (u32 *)h->staged.mflags;
-    a.gmark = h->gmark;
-    a.epoch = h->epoch;
-    a.list = h->list;
-    a.counters = h->counters;
-    a.clr = clr;
-    return a;
+    const RgMsgs &m = h->staged; // (the engine-owned message columns)
+    return RgIngest{rec, n, h->G, h->stride, h->P, (u64 *)m.mi, (u64 *)m.mc, (u64 *)m.mh, (u64 *)m.mrs, (u64 *)m.mlt, (u32 *)m.mflags,
+                    h->gmark, h->epoch, h->list, h->counters, clr};
 }
 
 // Two {touched groups, dropped records} counter pairs take turns: a sparse tick uses one, the ingest kernel of the same
 // window resets the other for the tick after it, rg_ctr_flip switches -- no memset command per tick.
 static u32 *rg_ctr_other(rg_engine *h) { return h->counters == h->counters_base ? h->counters_base + 2 : h->counters_base; }
 static void rg_ctr_flip(rg_engine *h) { h->counters = rg_ctr_other(h); }
+
+// What an ingest kernel clears on its way: the other counter pair, and with `results` the out words of the PREVIOUS sparse
+// tick's groups as well (the tick behind it then needs no k_clear_out).
+static RgClear rg_prev_clear(rg_engine *h, bool results) {
+    if (!results) return RgClear{nullptr, nullptr, 0u, rg_ctr_other(h)};
+    return RgClear{h->res_list, h->st.out, (u32)h->last_sparse_n, rg_ctr_other(h)};
+}
+static void rg_launch_ingest(rg_engine *h, const rg_wire_msg *rec, u64 n, const RgClear &clr) {
+    hipLaunchKernelGGL(k_ingest, dim3(rg_grid(n, RG_INGEST_BLOCK)), dim3(RG_INGEST_BLOCK), 0, h->stream, rg_ingest_args(h, rec, n, clr));
+}
+// the staged message columns as a list tick reads them (mhr: the hints as they came, until a resolve pass says otherwise)
+static RgMsgs rg_staged_msgs(rg_engine *h) {
+    RgMsgs ms = h->staged;
+    ms.mhr = ms.mh;
+    return ms;
+}
+// where a list tick gathers its results (also into `packed` when given)
+static RgListOut rg_list_out(rg_engine *h, char *packed) { return RgListOut{h->res_list, h->res_commit, h->res_out, packed}; }
+// where a send stage that runs inside a tick's launch puts its work items (device Inflights)
+static RgSmallSend rg_small_send(rg_engine *h, u64 max_entries, u32 flags) {
+    return RgSmallSend{h->ins, max_entries, flags, h->send_items, h->send_counter, h->pin_send};
+}
+// device staging for n records (+ one block: RG_INGEST_BLOCK)
+static int rg_reserve_records(rg_engine *h, u64 n) {
+    RG_HIP(rg_grow_dev(h, &h->d_records, &h->d_records_cap, n, 4096, sizeof(rg_wire_msg), RG_INGEST_BLOCK * sizeof(rg_wire_msg)));
+    return RG_OK;
+}
+// the packed results of up to `groups` groups: the device buffer and its pinned twin, one unit
+static int rg_reserve_packed(rg_engine *h, u64 groups) {
+    RG_HIP(rg_grow_pair(&h->d_packed, &h->pin_packed, &h->packed_cap, groups, (u64)4096, sizeof(rg_res_rec), RG_PACKED_HDR, rg_dev_alloc,
+                        rg_dev_free, rg_pin_alloc, rg_pin_free, [h] { return hipStreamSynchronize(h->stream); }));
+    return RG_OK;
+}
 
 int rg_ensure_sparse(rg_engine *h) {
     if (h->sparse_arena) return RG_OK;
@@ -53,22 +71,12 @@ static int rg_ingest_impl(rg_engine *h, const rg_wire_msg *records, u64 n, u64 *
     RG_ENTER_STEP(h, "rg_ingest");
     int rc = rg_ensure_sparse(h);
     if (rc) return rc;
-    if (n > h->d_records_cap) {
-        if (h->d_records) {
-            RG_HIP(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->d_records);
-            h->d_records = nullptr;
-        }
-        u64 cap = h->d_records_cap ? h->d_records_cap : 4096;
-        while (cap < n) cap *= 2;
-        RG_HIP(hipMalloc(&h->d_records, (cap + RG_INGEST_BLOCK) * sizeof(rg_wire_msg)));
-        h->d_records_cap = cap;
-    }
+    rc = rg_reserve_records(h, n);
+    if (rc) return rc;
     u32 dup0 = 0; // duplicates so far in this tick window (device ingests included)
     RG_HIP(hipMemcpyAsync(&dup0, h->counters + 1, 4, hipMemcpyDeviceToHost, h->stream));
     RG_HIP(hipMemcpyAsync(h->d_records, records, n * sizeof(rg_wire_msg), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(k_ingest, dim3(rg_grid(n, RG_INGEST_BLOCK)), dim3(RG_INGEST_BLOCK), 0, h->stream,
-                       rg_ingest_args(h, h->d_records, n, RgClear{nullptr, nullptr, 0u, rg_ctr_other(h)}));
+    rg_launch_ingest(h, h->d_records, n, rg_prev_clear(h, false));
     u32 dup = 0;
     RG_HIP(hipMemcpyAsync(&dup, h->counters + 1, 4, hipMemcpyDeviceToHost, h->stream));
     RG_HIP(hipStreamSynchronize(h->stream)); // the caller's record array may be reused after return
@@ -91,8 +99,7 @@ extern "C" int rg_ingest_device(rg_engine *h, const rg_wire_msg *dev_records, ui
     RG_ENTER_STEP(h, "rg_ingest_device");
     int rc = rg_ensure_sparse(h);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_ingest, dim3(rg_grid(n, RG_INGEST_BLOCK)), dim3(RG_INGEST_BLOCK), 0, h->stream,
-                       rg_ingest_args(h, dev_records, n, RgClear{nullptr, nullptr, 0u, rg_ctr_other(h)}));
+    rg_launch_ingest(h, dev_records, n, rg_prev_clear(h, false));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "rg_ingest_device: %s", hipGetErrorString(e));
     h->ingested_upper += n;
@@ -134,14 +141,9 @@ int rg_sparse_enqueue(rg_engine *h, u64 upper, char *packed, bool any_logterm, b
         h->hint_check_due = true;
         h->hint_probe_pending = false;
     }
-    RgMsgs ms = h->staged;
-    ms.mhr = ms.mh;
+    RgMsgs ms = rg_staged_msgs(h);
     u64 *mf = (u64 *)h->staged.mflags;
-    RgListOut lo; // the tick gathers its own results (one launch less than a separate gather kernel)
-    lo.rl = h->res_list;
-    lo.rc = h->res_commit;
-    lo.ro = h->res_out;
-    lo.packed = packed;
+    const RgListOut lo = rg_list_out(h, packed); // the tick gathers its own results (one launch less than a separate gather kernel)
     if (one_launch && small_send) { // ... and the touched groups' send stage as well (rg_flush_send)
         if (any_logterm) ms.mhr = h->rhint;
         h->launch->flush_small_send(h->stream, h->st, ms, h->any_group_commit, *one_launch, h->rhint, mf, lo, *small_send);
@@ -225,7 +227,6 @@ extern "C" int rg_ingested_results(rg_engine *h, uint64_t *groups, uint64_t *com
     return RG_OK;
 } RG_ABI_GUARD
 
-
 // ------------------------------------------------------------------------------------------------
 // host mirror of RawNode::step for MsgAppendResponse
 // ------------------------------------------------------------------------------------------------
@@ -280,29 +281,43 @@ static int rg_from_self(rg_engine *h, u64 group, int slot, bool *is_self) {
     return RG_OK;
 }
 
-extern "C" int rg_step(rg_engine *h, uint64_t group, const rg_append_response *m) try {
-    if (!h || !m || group >= h->G) return rg_fail(RG_ERR_INVALID_ARG, "rg_step: bad argument");
-    if (!h->host_mirror) return rg_fail(RG_ERR_STATE, "rg_step: rg_set_peers was never called");
-    // RawNode::step (src/raw_node.rs:402-411): MsgAppendResponse is not a local message type; a response from an id
-    // without a Progress is rejected BEFORE Raft::step looks at the term, so a removed peer cannot depose the leader
-    const int slot = rg_find_slot(h, group, m->from);
-    if (slot < 0) return rg_fail(RG_ERR_STEP_PEER_NOT_FOUND, "rg_step: peer %llu not in group %llu (raw_node.rs:407-410)",
-                                 (unsigned long long)m->from, (unsigned long long)group);
+static int rg_need_mirror(rg_engine *h, const char *who) {
+    return h->host_mirror ? RG_OK : rg_fail(RG_ERR_STATE, "%s: rg_set_peers was never called", who);
+}
+
+// What RawNode::step and Raft::step decide before step_leader sees a response from `from` with `term`: an error, a silent
+// drop (RG_OK, *slot = -1), or the peer's slot with nothing queued in it yet.
+static int rg_admit(rg_engine *h, u64 group, u64 from, u64 term, const char *who, int *slot) {
+    *slot = -1;
+    if (int rc = rg_need_mirror(h, who)) return rc;
+    // RawNode::step (src/raw_node.rs:402-411): a response is not a local message type; one from an id without a Progress is
+    // rejected BEFORE Raft::step looks at the term, so a removed peer cannot depose the leader
+    const int s = rg_find_slot(h, group, from);
+    if (s < 0) return rg_fail(RG_ERR_STEP_PEER_NOT_FOUND, "%s: peer %llu not in group %llu (raw_node.rs:407-410)", who,
+                              (unsigned long long)from, (unsigned long long)group);
     // Raft::step term gate (src/raft.rs:1282-1411); term 0 skips the gate (":1282 local message") and falls
     // through to step_leader exactly as in the reference
-    if (m->term != 0) {
-        if (m->term > h->terms[group])
-            return rg_fail(RG_ERR_HIGHER_TERM, "rg_step: message term %llu > leader term %llu: step down (raft.rs:1284-1348)",
-                           (unsigned long long)m->term, (unsigned long long)h->terms[group]);
-        if (m->term < h->terms[group]) return RG_OK; // stale term: ignored (raft.rs:1349-1411)
+    if (term != 0) {
+        if (term > h->terms[group])
+            return rg_fail(RG_ERR_HIGHER_TERM, "%s: message term %llu > leader term %llu: step down (raft.rs:1284-1348)", who,
+                           (unsigned long long)term, (unsigned long long)h->terms[group]);
+        if (term < h->terms[group]) return RG_OK; // stale term: ignored (raft.rs:1349-1411)
     }
     bool from_self;
-    int src = rg_from_self(h, group, slot, &from_self);
-    if (src) return src;
+    if (int rc = rg_from_self(h, group, s, &from_self)) return rc;
     if (from_self) return RG_OK; // (dropped: see rg_from_self)
+    if (h->q_mf[group * 8 + s] & (RG_MF_VALID | RG_MF_HEARTBEAT))
+        return rg_fail(RG_ERR_SLOT_BUSY, "%s: peer %llu already has a message queued; rg_flush first", who, (unsigned long long)from);
+    *slot = s;
+    return RG_OK;
+}
+
+extern "C" int rg_step(rg_engine *h, uint64_t group, const rg_append_response *m) try {
+    if (!h || !m || group >= h->G) return rg_fail(RG_ERR_INVALID_ARG, "rg_step: bad argument");
+    int slot;
+    const int arc = rg_admit(h, group, m->from, m->term, "rg_step", &slot);
+    if (arc || slot < 0) return arc;
     u8 &f = h->q_mf[group * 8 + slot];
-    if (f & (RG_MF_VALID | RG_MF_HEARTBEAT)) return rg_fail(RG_ERR_SLOT_BUSY, "rg_step: peer %llu already has a message queued; rg_flush first",
-                                        (unsigned long long)m->from);
     rg_touch(h, group);
     const size_t o = (size_t)slot * h->stride + group;
     h->q_mi[o] = m->index;
@@ -319,24 +334,12 @@ extern "C" int rg_step(rg_engine *h, uint64_t group, const rg_append_response *m
 extern "C" int rg_step_heartbeat_response(rg_engine *h, uint64_t group, uint64_t from, uint64_t term, uint64_t commit,
                                           uint8_t ins_full) try {
     if (!h || group >= h->G) return rg_fail(RG_ERR_INVALID_ARG, "rg_step_heartbeat_response: bad argument");
-    if (!h->host_mirror) return rg_fail(RG_ERR_STATE, "rg_step_heartbeat_response: rg_set_peers was never called");
-    const int slot = rg_find_slot(h, group, from); // raw_node.rs:407-410 comes before the term gate
-    if (slot < 0) return rg_fail(RG_ERR_STEP_PEER_NOT_FOUND, "rg_step_heartbeat_response: peer %llu not in group %llu",
-                                 (unsigned long long)from, (unsigned long long)group);
-    if (term != 0) {
-        if (term > h->terms[group]) return rg_fail(RG_ERR_HIGHER_TERM, "rg_step_heartbeat_response: higher term: step down");
-        if (term < h->terms[group]) return RG_OK;
-    }
-    bool from_self;
-    int src = rg_from_self(h, group, slot, &from_self);
-    if (src) return src;
-    if (from_self) return RG_OK; // (dropped: see rg_from_self)
-    u8 &f = h->q_mf[group * 8 + slot];
-    if (f & (RG_MF_VALID | RG_MF_HEARTBEAT))
-        return rg_fail(RG_ERR_SLOT_BUSY, "rg_step_heartbeat_response: peer %llu already has a message queued", (unsigned long long)from);
+    int slot;
+    const int arc = rg_admit(h, group, from, term, "rg_step_heartbeat_response", &slot);
+    if (arc || slot < 0) return arc;
     rg_touch(h, group);
     h->q_mc[(size_t)slot * h->stride + group] = commit;
-    f |= RG_MF_HEARTBEAT | (ins_full ? RG_MF_INS_FULL : 0);
+    h->q_mf[group * 8 + slot] |= RG_MF_HEARTBEAT | (ins_full ? RG_MF_INS_FULL : 0);
     return RG_OK;
 } RG_ABI_GUARD
 
@@ -355,7 +358,6 @@ static int rg_self_slot(rg_engine *h, u64 group, u32 *slot) {
     *slot = RG_CFG_SELF(h->host_cfg[group]);
     return RG_OK;
 }
-
 
 extern "C" int rg_step_bytes(rg_engine *h, uint64_t group, const uint8_t *bytes, uint64_t len, uint8_t ins_full) try {
     if (!h || group >= h->G) return rg_fail(RG_ERR_INVALID_ARG, "rg_step_bytes: bad argument");
@@ -389,7 +391,7 @@ extern "C" int rg_step_bytes(rg_engine *h, uint64_t group, const uint8_t *bytes,
 
 extern "C" int rg_local_append(rg_engine *h, uint64_t group, uint64_t new_last_index) try {
     if (!h || group >= h->G) return rg_fail(RG_ERR_INVALID_ARG, "rg_local_append: bad argument");
-    if (!h->host_mirror) return rg_fail(RG_ERR_STATE, "rg_local_append: rg_set_peers was never called");
+    if (int mrc = rg_need_mirror(h, "rg_local_append")) return mrc;
     u32 slot;
     int rc = rg_self_slot(h, group, &slot);
     if (rc) return rc;
@@ -401,7 +403,7 @@ extern "C" int rg_local_append(rg_engine *h, uint64_t group, uint64_t new_last_i
 
 extern "C" int rg_local_persisted(rg_engine *h, uint64_t group, uint64_t index) try {
     if (!h || group >= h->G) return rg_fail(RG_ERR_INVALID_ARG, "rg_local_persisted: bad argument");
-    if (!h->host_mirror) return rg_fail(RG_ERR_STATE, "rg_local_persisted: rg_set_peers was never called");
+    if (int mrc = rg_need_mirror(h, "rg_local_persisted")) return mrc;
     u32 slot;
     int rc = rg_self_slot(h, group, &slot);
     if (rc) return rc;
@@ -415,7 +417,7 @@ extern "C" int rg_local_persisted(rg_engine *h, uint64_t group, uint64_t index) 
 
 extern "C" int rg_local_become_leader(rg_engine *h, uint64_t group, uint64_t term) try {
     if (!h || group >= h->G) return rg_fail(RG_ERR_INVALID_ARG, "rg_local_become_leader: bad argument");
-    if (!h->host_mirror) return rg_fail(RG_ERR_STATE, "rg_local_become_leader: rg_set_peers was never called");
+    if (int mrc = rg_need_mirror(h, "rg_local_become_leader")) return mrc;
     if (term <= h->terms[group])
         return rg_fail(RG_ERR_INVALID_ARG, "rg_local_become_leader: term %llu is not above the group's term %llu",
                        (unsigned long long)term, (unsigned long long)h->terms[group]);
@@ -440,7 +442,7 @@ extern "C" int rg_local_become_leader(rg_engine *h, uint64_t group, uint64_t ter
 // RawNode::report_unreachable / report_snapshot (src/raw_node.rs:692-709): MsgUnreachable / MsgSnapStatus stepped at a leader
 static int rg_report(rg_engine *h, uint64_t group, uint64_t peer_id, u32 kind, const char *who) {
     if (!h || group >= h->G) return rg_fail(RG_ERR_INVALID_ARG, "%s: bad argument", who);
-    if (!h->host_mirror) return rg_fail(RG_ERR_STATE, "%s: rg_set_peers was never called", who);
+    if (int mrc = rg_need_mirror(h, who)) return mrc;
     const int slot = rg_find_slot(h, group, peer_id);
     if (slot < 0) return RG_OK; // "no progress available for {}": ignored (the reference drops the step's result as well)
     u64 row = 0;
@@ -459,7 +461,7 @@ extern "C" int rg_report_snapshot(rg_engine *h, uint64_t group, uint64_t peer_id
 
 extern "C" int rg_mark_sent(rg_engine *h, uint64_t group, uint64_t peer_id) try {
     if (!h || group >= h->G) return rg_fail(RG_ERR_INVALID_ARG, "rg_mark_sent: bad argument");
-    if (!h->host_mirror) return rg_fail(RG_ERR_STATE, "rg_mark_sent: rg_set_peers was never called");
+    if (int mrc = rg_need_mirror(h, "rg_mark_sent")) return mrc;
     const int slot = rg_find_slot(h, group, peer_id);
     if (slot < 0) return rg_fail(RG_ERR_STEP_PEER_NOT_FOUND, "rg_mark_sent: peer %llu not in group %llu",
                                  (unsigned long long)peer_id, (unsigned long long)group);
@@ -472,31 +474,201 @@ extern "C" int rg_mark_sent(rg_engine *h, uint64_t group, uint64_t peer_id) try 
     return RG_OK;
 } RG_ABI_GUARD
 
-// One sparse tick in ONE host<->device round trip: records (the caller's, or built from the mirror's queues when
-// `recs` is NULL) -> pinned staging -> ingest / clear / hint resolve / tick / gather back to back -> one packed D2H
-// copy of (groups, duplicates, {group, commit, out}...) -> one synchronisation. Results stay cached on the host.
-struct rg_send_req { // run the send stage inside the same round trip (engines with device Inflights)
-    u64 max_entries;
-    u32 flags;
-};
-
-static int rg_sparse_threecall(rg_engine *h, const rg_wire_msg *recs, u64 n, u32 *dup_out, const rg_send_req *send) {
+static int rg_sparse_threecall(rg_engine *h, const rg_wire_msg *recs, u64 n, u32 *dup_out, const RgSendReq *send) {
     // big batches are throughput-bound, not latency-bound: the packed copy (one slot per RECORD, not per group)
     // and the host-side unpacking cost more than two extra synchronisations (profiles/r01_sparse_path...)
     // (the drops of the WHOLE window, device-side ingests included, as on the round-trip roads: read behind this call's
     // ingest kernel, before the tick flips the counter pair)
     u64 d64 = 0;
-    uint64_t ng = 0;
     int rc = rg_ingest_impl(h, recs, n, nullptr, &d64);
-    if (rc == RG_OK) rc = rg_tick_ingested(h, &ng);
+    if (rc == RG_OK) rc = rg_tick_ingested(h, nullptr);
     if (rc == RG_OK && send) rc = rg_send_appends(h, send->max_entries, send->flags);
     if (dup_out) *dup_out = (u32)d64;
     return rc;
 }
 
-static int rg_mailbox_flush(rg_engine *h, u64 n, bool any_logterm, bool *served, const rg_send_req *send);
+// What crosses the steps of one rg_sparse_roundtrip.
+struct RgFlushRun {
+    u64 n;            // records staged in pin_records
+    u64 upper;        // bound of the groups the tick walked (0: nothing was walked)
+    u32 n_groups, dup; // what the device answered: groups ticked, records dropped in this window
+    bool fetch_items; // a send request's work items came back through pin_send
+    bool served;      // the resident mailbox workgroup took the flush
+};
+
+// Step 1, staging: the caller's records, or those built from the mirror's queues when `recs` is NULL, into pin_records.
+static int rg_flush_stage(rg_engine *h, const rg_wire_msg *recs, u64 n, const RgSendReq *send, RgFlushRun *r) {
+    if (!recs) {
+        n = 0;
+        for (u64 g : h->q_dirty)
+            for (u32 p = 0; p < h->P; p++) n += h->q_mf[g * 8 + p] != 0;
+    }
+    r->n = n;
+    if (n > RG_INGEST_BLOCK || (send && !h->ins_arena)) { // not a flush the resident mailbox workgroup can serve: it leaves
+        int rc = rg_mailbox_quiesce(h);                     // now, before anything below waits for the stream or replaces
+        if (rc) return rc;                                  // a buffer it reads
+    }
+    RG_HIP(rg_grow_pin(h, &h->pin_records, &h->pin_records_cap, n, 4096, sizeof(rg_wire_msg)));
+    if (recs) {
+        if (n) memcpy(h->pin_records, recs, n * sizeof(rg_wire_msg));
+        return RG_OK;
+    }
+    u64 k = 0;
+    for (u64 g : h->q_dirty) {
+        for (u32 p = 0; p < h->P; p++) {
+            const u8 f = h->q_mf[g * 8 + p];
+            if (!f) continue;
+            const size_t o = (size_t)p * h->stride + g;
+            rg_wire_msg &m = h->pin_records[k++];
+            m.group = g;
+            m.index = h->q_mi[o];
+            m.commit = h->q_mc[o];
+            m.hint = h->q_mh[o];
+            m.rs = h->q_mrs[o];
+            m.log_term = h->q_mlt[o];
+            m.slot = p;
+            m.flags = f;
+            m.pad = 0;
+        }
+    }
+    return RG_OK;
+}
+
+// Step 2, the resident mailbox kernel, when it is on: no launch, no synchronisation (rg_mailbox_flush says whether it took
+// the flush). When it did not, it is told to leave: the flush goes through launches on the stream.
+static int rg_mailbox_flush(rg_engine *h, u64 n, bool any_logterm, bool *served, const RgSendReq *send);
+static int rg_flush_mailbox(rg_engine *h, bool any_logterm, const RgSendReq *send, RgFlushRun *r) {
+    if (h->mbox_on) {
+        int rc = rg_mailbox_flush(h, r->n, any_logterm, &r->served, send);
+        if (rc) return rc;
+    }
+    if (!r->served) return rg_mailbox_quiesce(h);
+    h->out_is_dense = false; // (what rg_sparse_enqueue records)
+    h->tick_launches++;
+    rg_ctr_flip(h);
+    r->n_groups = reinterpret_cast<const u32 *>(h->pin_packed)[0];
+    r->dup = reinterpret_cast<const u32 *>(h->pin_packed)[1];
+    if (send) { // the request ran the stage of every touched group: its items are in pin_send (rg_tick_send_listed)
+        r->upper = r->n; // (only "something was walked", in rg_flush_collect)
+        r->fetch_items = true;
+    }
+    return RG_OK;
+}
+
+// The send stage of a request that did not run inside the tick's launch rides behind it: it walks the gathered list, whose
+// length is still only on the device. Small ones bring count and items back with the tick's results (*fetch_items).
+static int rg_flush_ride_send(rg_engine *h, const RgSendReq *send, u64 upper, bool *fetch_items) {
+    const u64 item_bound = upper * h->P;
+    int rc = rg_send_enqueue(h, send->max_entries, send->flags, h->res_list, upper, h->counters);
+    if (rc) return rc;
+    *fetch_items = item_bound <= RG_SEND_SPEC;
+    if (!*fetch_items) return RG_OK;
+    rc = rg_ensure_pin_send(h);
+    if (rc) return rc;
+    RG_HIP(hipMemcpyAsync(h->pin_send, h->send_counter, 4, hipMemcpyDeviceToHost, h->stream));
+    RG_HIP(hipMemcpyAsync(h->pin_send + 16, h->send_items, item_bound * sizeof(rg_send_item), hipMemcpyDeviceToHost, h->stream));
+    return RG_OK;
+}
+
+// Step 3, the launch road: ingest, rg_sparse_enqueue, the send stage, ONE synchronisation.
+static int rg_flush_launch(rg_engine *h, bool any_logterm, const RgSendReq *send, RgFlushRun *r) {
+    const u64 n = r->n;
+    int rc = rg_reserve_records(h, n);
+    if (rc) return rc;
+    const u64 upper_all = h->ingested_upper + n; // device ingests of this window count too
+    const u64 upper = r->upper = upper_all < h->G ? upper_all : h->G;
+    rc = rg_reserve_packed(h, upper);
+    if (rc) return rc;
+    // Small batches are latency-bound: every HIP call costs the host 3-5 us. The kernels then read the records straight
+    // out of the pinned staging buffer and write the packed results straight into pinned host memory (both are mapped into
+    // the device's address space; a few KB over PCIe inside a kernel cost less than a copy command each way), and the
+    // ingest kernel also zeroes the previous sparse tick's result words: ingest + tick + counter reset + ONE
+    // synchronisation instead of copy, ingest, clear, tick, copy, reset, synchronisation.
+    const bool zero_copy = n && upper <= RG_ZEROCOPY_MAX;
+    // (with device Inflights and an unconsumed send stage the previous result words are still needed: rg_settle_send)
+    const bool settle_due = h->ins_arena && h->send_ready;
+    // ... and up to one workgroup's worth of records the whole flush is ONE launch (k_flush_small)
+    const bool one_launch = zero_copy && n <= RG_INGEST_BLOCK && !settle_due;
+    const bool out_cleared = zero_copy && !h->out_is_dense && !settle_due;
+    const RgClear clr = rg_prev_clear(h, out_cleared);
+    RgIngest fused_args;
+    if (one_launch) {
+        fused_args = rg_ingest_args(h, h->pin_records, n, clr);
+    } else if (n) {
+        const rg_wire_msg *src = h->pin_records;
+        if (!zero_copy) {
+            RG_HIP(hipMemcpyAsync(h->d_records, h->pin_records, n * sizeof(rg_wire_msg), hipMemcpyHostToDevice, h->stream));
+            src = h->d_records;
+        }
+        rg_launch_ingest(h, src, n, clr);
+    }
+    // One launch AND a send request: the stage of every touched group runs behind its tick inside k_flush_small_send, on the
+    // tick's registers; its work items land in the device list and, through the mapped pinned buffer, in host memory.
+    const bool stage_inside = one_launch && send;
+    RgSmallSend small_send;
+    if (stage_inside) {
+        rc = rg_ensure_pin_send(h);
+        if (rc) return rc;
+        small_send = rg_small_send(h, send->max_entries, send->flags);
+        rg_list_stage_ran(h, send->max_entries, send->flags);
+    }
+    // (records ingested on the device in this window may carry log terms the host has not seen)
+    rc = rg_sparse_enqueue(h, upper, zero_copy ? h->pin_packed : h->d_packed, any_logterm || h->ingested_upper != 0, out_cleared,
+                           one_launch ? &fused_args : nullptr, stage_inside ? &small_send : nullptr);
+    if (rc) return rc;
+    r->fetch_items = stage_inside && upper;
+    if (send && upper && !stage_inside) {
+        rc = rg_flush_ride_send(h, send, upper, &r->fetch_items);
+        if (rc) return rc;
+    }
+    if (!upper) return RG_OK;
+    if (!zero_copy)
+        RG_HIP(hipMemcpyAsync(h->pin_packed, h->d_packed, RG_PACKED_HDR + upper * sizeof(rg_res_rec), hipMemcpyDeviceToHost, h->stream));
+    RG_HIP(hipStreamSynchronize(h->stream));
+    rg_ctr_flip(h); // (the next window's pair was reset by this window's ingest kernel)
+    r->n_groups = reinterpret_cast<const u32 *>(h->pin_packed)[0];
+    r->dup = reinterpret_cast<const u32 *>(h->pin_packed)[1];
+    return RG_OK;
+}
+
+// Step 4, collecting: the tick's bookkeeping, the send stage's, and the packed results into the host caches.
+static int rg_flush_collect(rg_engine *h, const RgSendReq *send, const RgFlushRun &r) {
+    int rc = rg_sparse_finish(h, r.n_groups);
+    if (rc) return rc;
+    if (send) {
+        h->send_ready = false; // the stage of this tick has run (or had nothing to walk)
+        h->send_bound = (u64)r.n_groups * h->P;
+        if (!r.upper) {
+            RG_HIP(hipMemsetAsync(h->send_counter, 0, 4, h->stream));
+            h->host_items.clear();
+            h->host_items_valid = true;
+        } else if (r.fetch_items) {
+            const u32 cnt = *reinterpret_cast<const u32 *>(h->pin_send);
+            const rg_send_item *it = reinterpret_cast<const rg_send_item *>(h->pin_send + 16);
+            h->host_items.assign(it, it + cnt);
+            h->host_items_valid = true;
+        }
+    }
+    const rg_res_rec *rec = reinterpret_cast<const rg_res_rec *>(h->pin_packed + RG_PACKED_HDR);
+    h->host_res_groups.resize(r.n_groups);
+    h->host_res_commit.resize(r.n_groups);
+    h->host_res_out.resize(r.n_groups);
+    for (u32 i = 0; i < r.n_groups; i++) {
+        h->host_res_groups[i] = rec[i].group;
+        h->host_res_commit[i] = rec[i].commit;
+        h->host_res_out[i] = rec[i].out;
+    }
+    h->host_res_valid = true;
+    return RG_OK;
+}
+
+// One sparse tick in ONE host<->device round trip: records (the caller's, or built from the mirror's queues when
+// `recs` is NULL) -> pinned staging -> ingest / clear / hint resolve / tick / gather back to back -> one packed D2H
+// copy of (groups, duplicates, {group, commit, out}...) -> one synchronisation. Results stay cached on the host.
+// `send`: run the send stage inside the same round trip (engines with device Inflights). The roads: three calls (big
+// batches), the mailbox, and the launches of rg_flush_launch (one launch, with or without the stage; zero-copy or copied list).
 static int rg_sparse_roundtrip(rg_engine *h, const rg_wire_msg *recs, u64 n, bool any_logterm, u32 *dup_out,
-                               const rg_send_req *send = nullptr) {
+                               const RgSendReq *send = nullptr) {
     RG_HIP(hipSetDevice(h->cfg.device)); // (not RG_ENTER: this is the one path the resident mailbox kernel serves)
     int rc;
     if (h->ins_arena && h->hint_check_due) { // (rare: a log-term tick came before; the check needs the stream to itself)
@@ -508,216 +680,15 @@ static int rg_sparse_roundtrip(rg_engine *h, const rg_wire_msg *recs, u64 n, boo
     rc = rg_ensure_sparse(h);
     if (rc) return rc;
     if (recs && n > RG_ROUNDTRIP_MAX) return rg_sparse_threecall(h, recs, n, dup_out, send);
-    if (!recs) {
-        n = 0;
-        for (u64 g : h->q_dirty)
-            for (u32 p = 0; p < h->P; p++) n += h->q_mf[g * 8 + p] != 0;
-    }
-    if (n > RG_INGEST_BLOCK || (send && !h->ins_arena)) { // not a flush the resident mailbox workgroup can serve: it leaves
-        rc = rg_mailbox_quiesce(h);                         // now, before anything below waits for the stream or replaces
-        if (rc) return rc;                                  // a buffer it reads
-    }
-    if (n > h->pin_records_cap) {
-        if (h->pin_records) {
-            RG_HIP(hipStreamSynchronize(h->stream));
-            (void)hipHostFree(h->pin_records);
-            h->pin_records = nullptr;
-        }
-        u64 cap = 4096;
-        while (cap < n) cap *= 2;
-        RG_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->pin_records), cap * sizeof(rg_wire_msg), hipHostMallocDefault));
-        h->pin_records_cap = cap;
-    }
-    if (recs) {
-        if (n) memcpy(h->pin_records, recs, n * sizeof(rg_wire_msg));
-    } else {
-        u64 k = 0;
-        for (u64 g : h->q_dirty) {
-            for (u32 p = 0; p < h->P; p++) {
-                const u8 f = h->q_mf[g * 8 + p];
-                if (!f) continue;
-                const size_t o = (size_t)p * h->stride + g;
-                rg_wire_msg &r = h->pin_records[k++];
-                r.group = g;
-                r.index = h->q_mi[o];
-                r.commit = h->q_mc[o];
-                r.hint = h->q_mh[o];
-                r.rs = h->q_mrs[o];
-                r.log_term = h->q_mlt[o];
-                r.slot = p;
-                r.flags = f;
-                r.pad = 0;
-            }
-        }
-        if (n > RG_ROUNDTRIP_MAX) return rg_sparse_threecall(h, h->pin_records, n, dup_out, send);
-    }
-    // the resident mailbox kernel, when it is on: no launch, no synchronisation (rg_mailbox_flush says whether it took it)
-    bool served = false;
-    if (h->mbox_on) {
-        rc = rg_mailbox_flush(h, n, any_logterm, &served, send);
-        if (rc) return rc;
-    }
-    if (!served) {
-        rc = rg_mailbox_quiesce(h); // this flush goes through launches on the stream
-        if (rc) return rc;
-    }
-    u32 n_groups = 0, dup = 0;
-    u64 upper = 0;
-    bool fetch_items = false;
-    if (served) {
-        h->out_is_dense = false; // (what rg_sparse_enqueue records)
-        h->tick_launches++;
-        rg_ctr_flip(h);
-        n_groups = reinterpret_cast<const u32 *>(h->pin_packed)[0];
-        dup = reinterpret_cast<const u32 *>(h->pin_packed)[1];
-        if (send) { // the request ran the stage of every touched group: its items are in pin_send (rg_tick_send_listed)
-            upper = n; // (only "something was walked", below)
-            fetch_items = true;
-            h->send_cols_fresh = false;
-            h->send_last_dense = false;
-            h->host_items_valid = false;
-        }
-    } else {
-    if (n > h->d_records_cap) {
-        if (h->d_records) {
-            RG_HIP(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->d_records);
-            h->d_records = nullptr;
-        }
-        u64 cap = h->d_records_cap ? h->d_records_cap : 4096;
-        while (cap < n) cap *= 2;
-        RG_HIP(hipMalloc(&h->d_records, (cap + RG_INGEST_BLOCK) * sizeof(rg_wire_msg)));
-        h->d_records_cap = cap;
-    }
-    const u64 upper_all = h->ingested_upper + n; // device ingests of this window count too
-    upper = upper_all < h->G ? upper_all : h->G;
-    if (upper > h->packed_cap) {
-        if (h->d_packed) {
-            RG_HIP(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->d_packed);
-            (void)hipHostFree(h->pin_packed);
-            h->d_packed = h->pin_packed = nullptr;
-        }
-        u64 cap = 4096;
-        while (cap < upper) cap *= 2;
-        RG_HIP(hipMalloc(&h->d_packed, RG_PACKED_HDR + cap * sizeof(rg_res_rec)));
-        RG_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->pin_packed), RG_PACKED_HDR + cap * sizeof(rg_res_rec),
-                             hipHostMallocDefault));
-        h->packed_cap = cap;
-    }
-    // Small batches are latency-bound: every HIP call costs the host 3-5 us. The kernels then read the records straight
-    // out of the pinned staging buffer and write the packed results straight into pinned host memory (both are mapped into
-    // the device's address space; a few KB over PCIe inside a kernel cost less than a copy command each way), and the
-    // ingest kernel also zeroes the previous sparse tick's result words: ingest + tick + counter reset + ONE
-    // synchronisation instead of copy, ingest, clear, tick, copy, reset, synchronisation.
-    const bool zero_copy = n && upper <= RG_ZEROCOPY_MAX;
-    // ... and up to one workgroup's worth of records the whole flush is ONE launch (k_flush_small)
-    const bool one_launch = zero_copy && n <= RG_INGEST_BLOCK && !(h->ins_arena && h->send_ready);
-    bool out_cleared = false;
-    RgIngest fused_args;
-    if (one_launch) {
-        RgClear clr = {nullptr, nullptr, 0u, rg_ctr_other(h)};
-        if (!h->out_is_dense) {
-            clr.list = h->res_list;
-            clr.out = h->st.out;
-            clr.n = (u32)h->last_sparse_n;
-            out_cleared = true;
-        }
-        fused_args = rg_ingest_args(h, h->pin_records, n, clr);
-    } else if (n) {
-        RgClear clr = {nullptr, nullptr, 0u, rg_ctr_other(h)};
-        // (with device Inflights and an unconsumed send stage the previous result words are still needed: rg_settle_send)
-        if (zero_copy && !h->out_is_dense && !(h->ins_arena && h->send_ready)) {
-            clr.list = h->res_list;
-            clr.out = h->st.out;
-            clr.n = (u32)h->last_sparse_n;
-            out_cleared = true;
-        }
-        const rg_wire_msg *src = h->pin_records;
-        if (!zero_copy) {
-            RG_HIP(hipMemcpyAsync(h->d_records, h->pin_records, n * sizeof(rg_wire_msg), hipMemcpyHostToDevice, h->stream));
-            src = h->d_records;
-        }
-        hipLaunchKernelGGL(k_ingest, dim3(rg_grid(n, RG_INGEST_BLOCK)), dim3(RG_INGEST_BLOCK), 0, h->stream,
-                           rg_ingest_args(h, src, n, clr));
-    }
-    // (records ingested on the device in this window may carry log terms the host has not seen)
-    // One launch AND a send request: the stage of every touched group runs behind its tick inside k_flush_small_send, on the
-    // tick's registers; its work items land in the device list and, through the mapped pinned buffer, in host memory.
-    const bool stage_inside = one_launch && send;
-    RgSmallSend small_send;
-    if (stage_inside) {
-        if (!h->pin_send)
-            RG_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->pin_send), 16 + RG_SEND_SPEC * sizeof(rg_send_item),
-                                 hipHostMallocDefault));
-        small_send.ins = h->ins;
-        small_send.max_entries = send->max_entries;
-        small_send.flags = send->flags;
-        h->stage_max_entries = send->max_entries;
-        h->stage_flags = send->flags;
-        small_send.items = h->send_items;
-        small_send.counter = h->send_counter;
-        small_send.pin = h->pin_send;
-        h->send_cols_fresh = false; // (what rg_send_enqueue records for a stage over a list)
-        h->send_last_dense = false;
-        h->host_items_valid = false;
-    }
-    rc = rg_sparse_enqueue(h, upper, zero_copy ? h->pin_packed : h->d_packed, any_logterm || h->ingested_upper != 0, out_cleared,
-                           one_launch ? &fused_args : nullptr, stage_inside ? &small_send : nullptr);
+    RgFlushRun r = {};
+    rc = rg_flush_stage(h, recs, n, send, &r);
     if (rc) return rc;
-    // the send stage rides along: it walks the gathered list, whose length is still only on the device
-    const u64 item_bound = upper * h->P;
-    fetch_items = send && upper && (stage_inside || item_bound <= RG_SEND_SPEC);
-    if (send && upper && !stage_inside) {
-        rc = rg_send_enqueue(h, send->max_entries, send->flags, h->res_list, upper, h->counters);
-        if (rc) return rc;
-        if (fetch_items) {
-            if (!h->pin_send)
-                RG_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->pin_send), 16 + RG_SEND_SPEC * sizeof(rg_send_item),
-                                     hipHostMallocDefault));
-            RG_HIP(hipMemcpyAsync(h->pin_send, h->send_counter, 4, hipMemcpyDeviceToHost, h->stream));
-            RG_HIP(hipMemcpyAsync(h->pin_send + 16, h->send_items, item_bound * sizeof(rg_send_item), hipMemcpyDeviceToHost,
-                                  h->stream));
-        }
-    }
-    if (upper) {
-        if (!zero_copy)
-            RG_HIP(hipMemcpyAsync(h->pin_packed, h->d_packed, RG_PACKED_HDR + upper * sizeof(rg_res_rec), hipMemcpyDeviceToHost,
-                                  h->stream));
-        RG_HIP(hipStreamSynchronize(h->stream));
-        rg_ctr_flip(h); // (the next window's pair was reset by this window's ingest kernel)
-        n_groups = reinterpret_cast<const u32 *>(h->pin_packed)[0];
-        dup = reinterpret_cast<const u32 *>(h->pin_packed)[1];
-    }
-    } // (!served)
-    rc = rg_sparse_finish(h, n_groups);
-    if (rc) return rc;
-    if (send) {
-        h->send_ready = false; // the stage of this tick has run (or had nothing to walk)
-        h->send_bound = (u64)n_groups * h->P;
-        if (!upper) RG_HIP(hipMemsetAsync(h->send_counter, 0, 4, h->stream));
-        if (!upper) {
-            h->host_items.clear();
-            h->host_items_valid = true;
-        } else if (fetch_items) {
-            const u32 cnt = *reinterpret_cast<const u32 *>(h->pin_send);
-            const rg_send_item *it = reinterpret_cast<const rg_send_item *>(h->pin_send + 16);
-            h->host_items.assign(it, it + cnt);
-            h->host_items_valid = true;
-        }
-    }
-    if (dup_out) *dup_out = dup;
-    const rg_res_rec *rec = reinterpret_cast<const rg_res_rec *>(h->pin_packed + RG_PACKED_HDR);
-    h->host_res_groups.resize(n_groups);
-    h->host_res_commit.resize(n_groups);
-    h->host_res_out.resize(n_groups);
-    for (u32 i = 0; i < n_groups; i++) {
-        h->host_res_groups[i] = rec[i].group;
-        h->host_res_commit[i] = rec[i].commit;
-        h->host_res_out[i] = rec[i].out;
-    }
-    h->host_res_valid = true;
-    return RG_OK;
+    if (r.n > RG_ROUNDTRIP_MAX) return rg_sparse_threecall(h, h->pin_records, r.n, dup_out, send);
+    rc = rg_flush_mailbox(h, any_logterm, send, &r);
+    if (rc == RG_OK && !r.served) rc = rg_flush_launch(h, any_logterm, send, &r);
+    if (rc == RG_OK) rc = rg_flush_collect(h, send, r);
+    if (rc == RG_OK && dup_out) *dup_out = r.dup;
+    return rc;
 }
 
 // ---- the resident small-batch path (rg_mailbox_start; kernel: k_mailbox in rg_tick_kernels.h) ----
@@ -735,25 +706,15 @@ int rg_mailbox_quiesce(rg_engine *h) {
 }
 
 static int rg_mailbox_launch(rg_engine *h) {
-    RgMsgs ms = h->staged;
-    ms.mhr = ms.mh;
-    RgListOut lo;
-    lo.rl = h->res_list;
-    lo.rc = h->res_commit;
-    lo.ro = h->res_out;
-    lo.packed = h->pin_packed;
+    const RgMsgs ms = rg_staged_msgs(h);
+    const RgListOut lo = rg_list_out(h, h->pin_packed);
     RgClear clr = {h->res_list, h->st.out, 0u, nullptr};
     const RgIngest a0 = rg_ingest_args(h, h->pin_records, 0, clr);
     u64 *mf = (u64 *)h->staged.mflags;
     const u64 max_ticks = RG_MBOX_MAX_US * RG_MBOX_TICKS_PER_US;
     RgSmallSend ss0; // where a request's send stage (rg_flush_send) puts its work items; limit and flags come with the request
     memset(&ss0, 0, sizeof(ss0));
-    if (h->ins_arena) {
-        ss0.ins = h->ins;
-        ss0.items = h->send_items;
-        ss0.counter = h->send_counter;
-        ss0.pin = h->pin_send;
-    }
+    if (h->ins_arena) ss0 = rg_small_send(h, 0, 0);
     h->launch->mailbox(h->stream, h->st, ms, h->any_group_commit, a0, h->counters_base, h->rhint, mf, lo, h->mbox, h->mbox_idle_ticks, max_ticks, ss0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "mailbox: launch failed: %s", hipGetErrorString(e));
@@ -764,7 +725,7 @@ static int rg_mailbox_launch(rg_engine *h) {
 
 // One small flush through the mailbox: the records are in h->pin_records already. Returns RG_OK with *served = false
 // when the request cannot go this way (the caller takes the launch path).
-static int rg_mailbox_flush(rg_engine *h, u64 n, bool any_logterm, bool *served, const rg_send_req *send) {
+static int rg_mailbox_flush(rg_engine *h, u64 n, bool any_logterm, bool *served, const RgSendReq *send) {
     *served = false;
     // the body clears the PREVIOUS sparse tick's result words itself; a dense predecessor needs a memset on the stream
     if (!h->mbox_on || h->pub || h->out_is_dense || h->ingested_upper || n == 0 || n > RG_INGEST_BLOCK ||
@@ -790,10 +751,7 @@ static int rg_mailbox_flush(rg_engine *h, u64 n, bool any_logterm, bool *served,
         int rc = rg_mailbox_quiesce(h);
         if (rc) return rc;
     }
-    if (send) {
-        h->stage_max_entries = send->max_entries;
-        h->stage_flags = send->flags;
-    }
+    if (send) rg_list_stage_ran(h, send->max_entries, send->flags); // (from here on the request is served, or the call fails)
     const u32 s = ++h->mbox_seq;
     // (RgMbox: three self-validating words, one 8-byte store each; the records in pin_records are older stores)
     const u32 w0 = (u32)n | ((h->counters == h->counters_base ? 0u : 1u) << 16) | ((any_logterm ? 1u : 0u) << 17) |
@@ -838,17 +796,10 @@ extern "C" int rg_mailbox_start(rg_engine *h, uint32_t idle_timeout_us) try {
         memset(h->mbox, 0, sizeof(RgMbox));
     }
     // the kernel's arguments are fixed at launch: the staging buffers it reads / writes have to exist at their final size
-    if (!h->pin_records) {
-        RG_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->pin_records), 4096 * sizeof(rg_wire_msg), hipHostMallocDefault));
-        h->pin_records_cap = 4096;
-    }
-    if (!h->pin_packed) {
-        RG_HIP(hipMalloc(&h->d_packed, RG_PACKED_HDR + 4096 * sizeof(rg_res_rec)));
-        RG_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->pin_packed), RG_PACKED_HDR + 4096 * sizeof(rg_res_rec), hipHostMallocDefault));
-        h->packed_cap = 4096;
-    }
-    if (h->ins_arena && !h->pin_send) // device Inflights: rg_flush_send's work items come back through this buffer
-        RG_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->pin_send), 16 + RG_SEND_SPEC * sizeof(rg_send_item), hipHostMallocDefault));
+    RG_HIP(rg_grow_pin(h, &h->pin_records, &h->pin_records_cap, 1, 4096, sizeof(rg_wire_msg)));
+    rc = rg_reserve_packed(h, 1);
+    if (rc == RG_OK && h->ins_arena) rc = rg_ensure_pin_send(h); // device Inflights: rg_flush_send's work items come back through it
+    if (rc) return rc;
     h->mbox_idle_ticks = (u64)(idle_timeout_us ? idle_timeout_us : 2000u) * RG_MBOX_TICKS_PER_US;
     h->mbox_on = true;
     return RG_OK;
@@ -868,7 +819,7 @@ extern "C" int rg_mailbox_stop(rg_engine *h) try {
     return RG_OK;
 } RG_ABI_GUARD
 
-static int rg_flush_sparse(rg_engine *h, const rg_send_req *send) {
+static int rg_flush_sparse(rg_engine *h, const RgSendReq *send) {
     u32 dup = 0;
     int rc = rg_sparse_roundtrip(h, nullptr, 0, h->q_any_logterm, &dup, send);
     if (rc) return rc;
@@ -925,8 +876,8 @@ static int rg_settle_elections(rg_engine *h, bool results_available) {
     return rc;
 }
 
-static int rg_flush_impl(rg_engine *h, const rg_send_req *send) {
-    if (!h->host_mirror) return rg_fail(RG_ERR_STATE, "rg_flush: rg_set_peers was never called");
+static int rg_flush_impl(rg_engine *h, const RgSendReq *send) {
+    if (int mrc = rg_need_mirror(h, "rg_flush")) return mrc;
     int rc;
     const u64 launches0 = h->tick_launches;
     if (h->q_dirty.size() * 2 >= h->G) {
@@ -940,12 +891,7 @@ static int rg_flush_impl(rg_engine *h, const rg_send_req *send) {
         m.m_logterm = h->q_any_logterm ? h->q_mlt.data() : nullptr;
         m.m_flags = h->q_mf.data();
         // (with a send request: the tick and its stage as ONE launch, k_tick_send)
-        if (send) {
-            const RgSendReq sr = {(u64)send->max_entries, (u32)send->flags};
-            rc = rg_tick_host_impl(h, &m, &sr);
-        } else {
-            rc = rg_tick(h, &m);
-        }
+        rc = send ? rg_tick_host_impl(h, &m, send) : rg_tick(h, &m);
         // rg_ingested_results must work after ANY flush: gather the dirty groups' results compactly
         if (rc == RG_OK) rc = rg_ensure_sparse(h);
         if (rc == RG_OK) {
@@ -988,15 +934,7 @@ extern "C" int rg_flush(rg_engine *h) try {
 
 extern "C" int rg_flush_send(rg_engine *h, uint64_t max_entries_per_msg, uint32_t flags) try {
     if (!h) return rg_fail(RG_ERR_INVALID_ARG, "rg_flush_send: null engine");
-    if (!h->ins_arena)
-        return rg_fail(RG_ERR_STATE, "rg_flush_send: engine created with max_inflight = 0 (Inflights are the host's)");
-    if (flags & ~(RG_SEND_SKIP_BCAST_COMMIT | RG_SEND_BYTES)) return rg_fail(RG_ERR_INVALID_ARG, "rg_flush_send: unknown flags %#x", flags);
-    if ((flags & RG_SEND_BYTES) && !h->esz)
-        return rg_fail(RG_ERR_STATE, "rg_flush_send: RG_SEND_BYTES needs the entry sizes (rg_log_sizes_enable)");
-    rg_send_req req;
-    req.max_entries = max_entries_per_msg;
-    req.flags = flags;
+    if (int src = rg_send_check(h, flags, "rg_flush_send")) return src;
+    const RgSendReq req = {(u64)max_entries_per_msg, (u32)flags};
     return rg_flush_impl(h, &req);
 } RG_ABI_GUARD
-
-

@@ -12,10 +12,7 @@ int rg_send_enqueue(rg_engine *h, uint64_t max_entries_per_msg, uint32_t flags, 
                            const u32 *n_ptr) {
     const bool append = (flags & RG_SEND_APPEND_LIST) != 0; // (rg_resolve_host_hints: the list keeps what it holds)
     flags &= ~RG_SEND_APPEND_LIST;
-    h->stage_max_entries = max_entries_per_msg;
-    h->stage_flags = flags & ~RG_SEND_REQUESTS_ONLY;
-    h->send_cols_fresh = false;
-    h->send_last_dense = false;
+    rg_list_stage_ran(h, max_entries_per_msg, flags & ~RG_SEND_REQUESTS_ONLY); // (the dense stage below says otherwise)
     if (!list && !n_ptr && n == h->G) { // every group: work items into the peer-major columns, no list
         const dim3 grid(rg_grid(h->G, RG_BLOCK)), block(RG_BLOCK);
         rg_with_p(h->P, [&](auto p) {
@@ -25,7 +22,6 @@ int rg_send_enqueue(rg_engine *h, uint64_t max_entries_per_msg, uint32_t flags, 
         if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "send stage: launch failed: %s", hipGetErrorString(e));
         h->send_cols_fresh = true;
         h->send_last_dense = true;
-        h->host_items_valid = false;
         return RG_OK;
     }
     if (!append) RG_HIP(hipMemsetAsync(h->send_counter, 0, 4, h->stream));
@@ -38,7 +34,23 @@ int rg_send_enqueue(rg_engine *h, uint64_t max_entries_per_msg, uint32_t flags, 
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "send stage: launch failed: %s", hipGetErrorString(e));
     }
+    return RG_OK;
+}
+
+// A send stage over a list of groups has run, or is about to, with this limit and these flags: its work items are in the
+// compact list (not in the dense stage's columns) and whatever the host fetched of an earlier stage is out of date.
+void rg_list_stage_ran(rg_engine *h, u64 max_entries, u32 flags) {
+    h->stage_max_entries = max_entries;
+    h->stage_flags = flags;
+    h->send_cols_fresh = false;
+    h->send_last_dense = false;
     h->host_items_valid = false;
+}
+
+// the pinned buffer a small stage's count and work items come back through in one round trip (rg_engine::pin_send)
+int rg_ensure_pin_send(rg_engine *h) {
+    if (h->pin_send) return RG_OK;
+    RG_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->pin_send), 16 + RG_SEND_SPEC * sizeof(rg_send_item), hipHostMallocDefault));
     return RG_OK;
 }
 
@@ -208,9 +220,8 @@ extern "C" int rg_send_items(rg_engine *h, rg_send_item *host_items, uint64_t ca
     // small stages (the sparse path): counter and items come back together through pinned memory -- one round trip
     const u64 spec = h->send_bound < cap ? h->send_bound : cap;
     if (spec && spec <= RG_SEND_SPEC) {
-        if (!h->pin_send)
-            RG_HIP(hipHostMalloc(reinterpret_cast<void **>(&h->pin_send), 16 + RG_SEND_SPEC * sizeof(rg_send_item),
-                                 hipHostMallocDefault));
+        const int prc = rg_ensure_pin_send(h);
+        if (prc) return prc;
         RG_HIP(hipMemcpyAsync(h->pin_send, h->send_counter, 4, hipMemcpyDeviceToHost, h->stream));
         RG_HIP(hipMemcpyAsync(h->pin_send + 16, h->send_items, spec * sizeof(rg_send_item), hipMemcpyDeviceToHost, h->stream));
         RG_HIP(hipStreamSynchronize(h->stream));
@@ -366,5 +377,3 @@ int rg_fix_ins_full(rg_engine *h) {
     if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "k_fix_ins_full launch failed: %s", hipGetErrorString(e));
     return RG_OK;
 }
-
-

@@ -44,7 +44,6 @@ const RgTickLaunch &rg_tick_launch(u32 P) {
     return *rg_with_p(P, [](auto p) { return &rg_tick_launch_p<decltype(p)::value>(); });
 }
 
-
 // (rg_create's failure paths and rg_destroy)
 void rg_drop(rg_engine *h) {
     if (h->counted_live) {
@@ -551,24 +550,12 @@ extern "C" int rg_restore(rg_engine *h) try {
     return rg_read_restore(h);
 } RG_ABI_GUARD
 
-
-
 extern "C" int rg_write_cells(rg_engine *h, const rg_cell_write *cells, uint64_t n) try {
     if (!h || (!cells && n)) return rg_fail(RG_ERR_INVALID_ARG, "rg_write_cells: bad argument");
     if (n == 0) return RG_OK;
     RG_ENTER(h);
-    if (n > h->d_cells_cap) { // engine-owned staging, grown geometrically (this call sits between ticks)
-        if (h->d_cells) {
-            RG_HIP(hipStreamSynchronize(h->stream));
-            (void)hipFree(h->d_cells);
-            h->d_cells = nullptr;
-            h->d_cells_cap = 0;
-        }
-        u64 cap = 1024;
-        while (cap < n) cap *= 2;
-        RG_HIP(hipMalloc(&h->d_cells, cap * sizeof(rg_cell_write)));
-        h->d_cells_cap = cap;
-    }
+    // engine-owned staging, grown geometrically (this call sits between ticks)
+    RG_HIP(rg_grow_dev(h, &h->d_cells, &h->d_cells_cap, (u64)n, 1024, sizeof(rg_cell_write)));
     RG_HIP(hipMemcpyAsync(h->d_cells, cells, n * sizeof(rg_cell_write), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_write_cells, dim3(rg_grid(n, 256)), dim3(256), 0, h->stream, h->st, h->d_cells, (u64)n, h->P,
                        h->ins.meta);
@@ -613,5 +600,3 @@ extern "C" int rg_set_config(rg_engine *h, uint64_t group, uint32_t cfg_word) tr
     if (!h->cls_stale && h->cls_on && rg_cfg_slots_named(cfg_word) > h->cls_host[group / RG_BLOCK]) h->cls_stale = true;
     return RG_OK;
 } RG_ABI_GUARD
-
-

@@ -29,6 +29,7 @@
 #include "rg_follow.h"
 
 #include "rg_tick_kernels.h"
+#include "rg_grow.h"
 
 // live engines of this process PER DEVICE: the Infinity Cache is one per device, and a range of ONE engine only stays
 // resident there (k_tick_split) while no other engine's traffic goes through it. Looked at ONCE, by rg_create, when the cache
@@ -235,7 +236,6 @@ struct rg_engine {
     std::vector<u64> q_mi, q_mc, q_mh, q_mrs, q_mlt; // [P][stride] host queues
     std::vector<u8> q_mf;                      // [G][8]
     std::vector<u64> q_dirty;                  // groups touched since the last flush
-    std::vector<rg_wire_msg> q_records;        // flush staging (wire-order records of the dirty groups)
     bool q_any_logterm;                        // some queued message carries Message.log_term
     struct RgQueuedElection { u64 group, old_term; };
     std::vector<RgQueuedElection> q_elections; // rg_local_become_leader calls of the pending flush: group, the term its gate had
@@ -296,8 +296,20 @@ static inline bool rg_col_per_run(int c) { return c == RG_COL_RUN_FIRST || c == 
 static inline void *rg_col(rg_engine *h, int c) { return h->arena + h->col_off[c]; }
 static inline unsigned rg_grid(u64 n, unsigned per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
+// rg_grow.h over HIP: a device or a pinned host staging buffer of the engine; the stream is drained before an old one goes
+static inline hipError_t rg_dev_alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+static inline hipError_t rg_pin_alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+static inline void rg_dev_free(void *p) { (void)hipFree(p); }
+static inline void rg_pin_free(void *p) { (void)hipHostFree(p); }
+template <typename T> static inline hipError_t rg_grow_dev(rg_engine *h, T **ptr, u64 *cap, u64 need, u64 first, size_t elem, size_t pad = 0) {
+    return rg_grow(ptr, cap, need, first, elem, pad, rg_dev_alloc, rg_dev_free, [h] { return hipStreamSynchronize(h->stream); });
+}
+template <typename T> static inline hipError_t rg_grow_pin(rg_engine *h, T **ptr, u64 *cap, u64 need, u64 first, size_t elem, size_t pad = 0) {
+    return rg_grow(ptr, cap, need, first, elem, pad, rg_pin_alloc, rg_pin_free, [h] { return hipStreamSynchronize(h->stream); });
+}
+
 #define RG_SEND_SPEC 16384 /* work items copied speculatively with their count (512 KB of pinned memory) */
-struct RgSendReq { // a tick that runs its send stage in the same launch (rg_tick_send, rg_tick_device_send)
+struct RgSendReq { // a tick or a flush that runs its send stage with it (rg_tick_send, rg_tick_device_send, rg_flush_send)
     u64 max_entries;
     u32 flags;
 };
@@ -316,6 +328,8 @@ int rg_tick_host_impl(rg_engine *h, const rg_msgs *m, const RgSendReq *send);
 int rg_send_enqueue(rg_engine *h, uint64_t max_entries_per_msg, uint32_t flags, const u64 *list, u64 n, const u32 *n_ptr);
 int rg_stage_records(rg_engine *h, const void *recs, size_t bytes);
 int rg_send_materialize(rg_engine *h);
+int rg_ensure_pin_send(rg_engine *h);
+void rg_list_stage_ran(rg_engine *h, u64 max_entries, u32 flags);
 int rg_fix_ins_full(rg_engine *h); // k_fix_ins_full over every group, on the engine's stream
 // abi_mirror.hip
 int rg_ensure_sparse(rg_engine *h);

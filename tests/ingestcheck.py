@@ -12,7 +12,7 @@ import fuzz
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# Which road rg_ingest_tick takes is decided by these three (raft_rs_amd/csrc/abi_mirror.hip, rg_sparse_roundtrip):
+# Which road rg_ingest_tick takes is decided by these three (raft_rs_amd/csrc/abi_mirror.hip, rg_sparse_roundtrip and rg_flush_launch):
 #   records <= RG_INGEST_BLOCK and window <= RG_ZEROCOPY_MAX   one launch (k_flush_small)
 #   window <= RG_ZEROCOPY_MAX                                  zero-copy: k_ingest reads pinned host memory, does RgClear's work
 #   records <= RG_ROUNDTRIP_MAX                                one round trip through device staging
