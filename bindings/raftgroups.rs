@@ -5,7 +5,7 @@
 use std::os::raw::{c_char, c_void};
 
 pub const RG_MAX_SLOTS: u32 = 8;
-pub const RG_ABI_VERSION: u32 = 10;
+pub const RG_ABI_VERSION: u32 = 11;
 pub const RG_PF_STATE_MASK: u32 = 0x03;
 pub const RG_STATE_PROBE: u32 = 0;
 pub const RG_STATE_REPLICATE: u32 = 1;
@@ -93,6 +93,17 @@ pub const RG_GATE_EV_HARD_STATE: u32 = 0x1;
 pub const RG_GATE_EV_BECAME_FOLLOWER: u32 = 0x2;
 pub const RG_GATE_EV_LEADER_CHANGED: u32 = 0x4;
 pub const RG_GATE_EV_CONF_CHECK: u32 = 0x8;
+pub const RG_ELECT_NONE: u32 = 0;
+pub const RG_ELECT_IGNORED: u32 = 1;
+pub const RG_ELECT_BLOCKED: u32 = 2;
+pub const RG_ELECT_REQUESTS: u32 = 3;
+pub const RG_ELECT_PENDING: u32 = 4;
+pub const RG_ELECT_LOST: u32 = 5;
+pub const RG_ELECT_WON: u32 = 6;
+pub const RG_ELECT_STEPPED_DOWN: u32 = 7;
+pub const RG_ELECT_REQ_TRANSFER: u32 = 0x1;
+pub const RG_CAMPAIGN_TIMEOUT_NOW: u32 = 0x1;
+pub const RG_CAMPAIGN_BLOCKED: u32 = 0x2;
 pub const RG_SEND_APPEND: u32 = 1;
 pub const RG_SEND_SNAPSHOT: u32 = 2;
 pub const RG_SEND_HOST: u32 = 3;
@@ -384,6 +395,79 @@ pub struct RgFollowGateResp {
 }
 
 #[repr(C)]
+pub struct RgFollowElect {
+    pub group: u64,
+    pub self_id: u64,
+    pub conf: u32,
+    pub yes: u8,
+    pub no: u8,
+    pub reserved: [u8; 2],
+}
+
+#[repr(C)]
+pub struct RgFollowElectResp {
+    pub term: u64,
+    pub req_term: u64,
+    pub req_index: u64,
+    pub req_log_term: u64,
+    pub req_commit: u64,
+    pub req_commit_term: u64,
+    pub result: u32,
+    pub events: u32,
+    pub req_kind: u32,
+    pub targets: u32,
+    pub status: u32,
+    pub flags: u32,
+}
+
+#[repr(C)]
+pub struct RgFollowElectOut {
+    pub result: *mut u8,
+    pub events: *mut u8,
+    pub status: *mut u8,
+    pub req_kind: *mut u8,
+    pub targets: *mut u8,
+    pub flags: *mut u8,
+    pub term: *mut u64,
+    pub req_term: *mut u64,
+    pub req_index: *mut u64,
+    pub req_log_term: *mut u64,
+    pub req_commit: *mut u64,
+    pub req_commit_term: *mut u64,
+}
+
+#[repr(C)]
+pub struct RgFollowCampaignReq {
+    pub group: u64,
+    pub term: u64,
+    pub from: u64,
+    pub flags: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+pub struct RgFollowVoteRec {
+    pub group: u64,
+    pub term: u64,
+    pub commit: u64,
+    pub commit_term: u64,
+    pub from_slot: u8,
+    pub kind: u8,
+    pub reject: u8,
+    pub reserved: [u8; 5],
+}
+
+#[repr(C)]
+pub struct RgFollowVoteCols {
+    pub kind: *const u8,
+    pub slot: *const u8,
+    pub reject: *const u8,
+    pub term: *const u64,
+    pub commit: *const u64,
+    pub commit_term: *const u64,
+}
+
+#[repr(C)]
 pub struct RgAppendResponse {
     pub from: u64,
     pub term: u64,
@@ -619,6 +703,13 @@ extern "C" {
     pub fn rg_follow_step_gated_device(h: *mut RgEngine, dev_msgs: *const RgFollowMsgs, dev_term: *const u64, dev_from: *const u64, dev_out: *const RgFollowOut, dev_gate: *mut u8, dev_events: *mut u8, dev_resp_term: *mut u64) -> i32;
     pub fn rg_follow_clock(h: *mut RgEngine, dev_hup: *mut u64, cap: u64, host_n: *mut u64) -> i32;
     pub fn rg_follow_clock_counts(h: *const RgEngine) -> *const u64;
+    pub fn rg_follow_elect_enable(h: *mut RgEngine) -> i32;
+    pub fn rg_follow_elect_write(h: *mut RgEngine, host: *const RgFollowElect, n: u64) -> i32;
+    pub fn rg_follow_elect_read(h: *mut RgEngine, host_groups: *const u64, n: u64, host_out: *mut RgFollowElect) -> i32;
+    pub fn rg_follow_campaign_device(h: *mut RgEngine, dev_groups: *const u64, dev_n: *const u64, cap: u64, dev_block: *const u8, dev_out: *const RgFollowElectOut) -> i32;
+    pub fn rg_follow_campaign(h: *mut RgEngine, host_reqs: *const RgFollowCampaignReq, n: u64, host_resp: *mut RgFollowElectResp) -> i32;
+    pub fn rg_follow_vote_resps(h: *mut RgEngine, host_recs: *const RgFollowVoteRec, n: u64, host_resp: *mut RgFollowElectResp) -> i32;
+    pub fn rg_follow_vote_resps_device(h: *mut RgEngine, dev_msgs: *const RgFollowVoteCols, dev_out: *const RgFollowElectOut) -> i32;
     pub fn rg_set_peers(h: *mut RgEngine, group: u64, peer_ids: *const u64, n: u32, term: u64) -> i32;
     pub fn rg_step(h: *mut RgEngine, group: u64, m: *const RgAppendResponse) -> i32;
     pub fn rg_step_heartbeat_response(h: *mut RgEngine, group: u64, from: u64, term: u64, commit: u64, ins_full: u8) -> i32;

@@ -41,7 +41,7 @@ extern "C" {
  * new members keep the old meaning), so a caller is compiled against the header of the library it loads. RG_ABI_VERSION is bumped
  * whenever a struct layout, an enum value or a signature changes; rg_abi_version() returns what the library was built with --
  * compare the two at start-up (raftgroups.hpp and the Python / Rust bindings do). */
-#define RG_ABI_VERSION 10u
+#define RG_ABI_VERSION 11u
 
 /* ---- status codes; the negative values mirror src/errors.rs:6-50 where one applies ----
  * Every entry point that returns int returns one of these and leaves the text in rg_last_error() (per thread). Nothing unwinds
@@ -717,8 +717,9 @@ int rg_follow_step_device(rg_engine *h, const rg_follow_msgs *dev_msgs, const rg
  *      src/raft_log.rs:412, :487, :637) ----
  * Optional, on top of the follower arena: per followed group the "soft" state of a non-leader -- term, leader_id, vote,
  * priority, role, promotable, election_elapsed and randomized_election_timeout. With it the arena answers every integer
- * question Raft::step asks of a non-leader; the host keeps bytes (entries, snapshots, contexts) and campaigning (hup, campaign,
- * vote responses, poll), MsgTimeoutNow, handle_snapshot / restore.
+ * question Raft::step asks of a non-leader; the host keeps bytes (entries, snapshots, contexts), handle_snapshot / restore and --
+ * unless rg_follow_elect_enable (the section after this one) puts them on the device too -- campaigning (hup, campaign, vote
+ * responses, poll) and MsgTimeoutNow.
  *   HOT cells: term u64, lead u64, clock u32 (election_elapsed in bits 0..14, promotable in bit 15, the randomized timeout in
  *   bits 16..31). COLD cells: vote u64, priority i64, role u8. 37 bytes per group of the stride. A steady append (equal term,
  *   unchanged leader) reads the three hot cells and writes the clock cell -- if election_elapsed was not 0 already.
@@ -813,6 +814,143 @@ int rg_follow_step_gated_device(rg_engine *h, const rg_follow_msgs *dev_msgs, co
 int rg_follow_clock(rg_engine *h, uint64_t *dev_hup, uint64_t cap, uint64_t *host_n);
 /* device u64 [2] the last rg_follow_clock wrote: [0] groups appended, [1] groups due; NULL before rg_follow_gate_enable */
 const uint64_t *rg_follow_clock_counts(const rg_engine *h);
+
+/* ---- The candidate half: campaign, vote responses and poll (Raft::hup, src/raft.rs:1472-1525; campaign, :1217-1263;
+ *      become_candidate / become_pre_candidate, :1101-1143; poll, :2166-2201; the vote responses of step_candidate, :2230-2244;
+ *      MsgTimeoutNow, :2245-2251, :2298-2318; maybe_commit_by_vote, :2126-2164; ProgressTracker::record_vote / tally_votes /
+ *      vote_result, src/tracker.rs:307-344; src/quorum/majority.rs:130-154; src/quorum/joint.rs:56-67) ----
+ * Optional, the third layer of the follower arena: per followed group the ELECTION cells, struct-of-arrays over the stride,
+ * 14 bytes per group:
+ *   self_id u64  Raft.id: the value written to `vote` and compared with leader_id.
+ *   conf    u32  voters.incoming as a slot bitmask in bits 0..7, voters.outgoing in bits 8..15 (0 = not joint), the group's own
+ *                slot in bits 16..18 -- the convention of RG_CFG_*; RG_ELECT_CONF_MAKE / _INCOMING / _OUTGOING / _SELF below.
+ *   votes   u16  ProgressTracker.votes: the `yes` slots in the low byte, the `no` slots in the high byte. record_vote keeps the
+ *                first vote of a slot (src/tracker.rs:307-309).
+ * With them the arena runs a whole election, from the timeout to "won: hand the group to the leader engine"; the host keeps
+ * bytes (entries, contexts, building the Messages from the request fields below) and the one question that needs entries:
+ * num_pending_conf (the BLOCKED bit of a campaign record, the dev_block column, RG_GATE_EV_CONF_CHECK).
+ * `promotable` stays in the clock cell of the gate: the host sets it when the configuration changes.
+ *   The votes need NO reset hook in the gate of the section above, which is why rg_follow_step*, rg_follow_step_gated*,
+ *   rg_follow_clock, rg_follow_soft_write / _read and their kernels are unchanged: the votes are read only while role !=
+ *   Follower; every transition INTO a candidate role on the device goes through campaign, which clears them
+ *   (become_pre_candidate :1134, reset :954); an rg_follow_soft_write to a candidate role leaves them to rg_follow_elect_write.
+ *   A group the gate made a Follower may keep stale bits in the cell: rg_follow_elect_read reports the votes of a Follower as 0,
+ *   which is what reset left in the reference.
+ * One RECORD is a MsgHup, a MsgTimeoutNow, a MsgRequestVoteResponse or a MsgRequestPreVoteResponse of one group. It is
+ * all-or-nothing: where the log status is RG_FOLLOW_HOST nothing of the three layers changed.
+ *   hup(transfer): a group whose leader_id == self_id is one this store LEADS: IGNORED. The pending-conf bit: BLOCKED, hup changed
+ *     nothing. Else campaign(TRANSFER for a MsgTimeoutNow, PRE_ELECTION under RG_GATE_PRE_VOTE, ELECTION).
+ *   campaign: become_pre_candidate (role, votes cleared, leader_id = 0) or become_candidate (reset(term + 1) -- a fresh
+ *     rg_follow_draw, election_elapsed = 0, leader_id = 0, votes cleared --, vote = self_id, role Candidate); poll(self, true);
+ *     if that did not win, REQUESTS: req_kind, req_term (term + 1 of a pre-vote), req_index = last_index, req_log_term =
+ *     last_term, req_commit / req_commit_term = commit_info(), targets = (incoming | outgoing) & ~self. RG_FOLLOW_HOST where
+ *     last_term or term(committed) lies in the dropped gap and the interval rule does not settle it.
+ *   poll(slot, granted): record_vote, then vote_result over the voters: an empty majority wins; a vote of a slot outside the
+ *     voters is recorded and not counted.
+ *       won as PreCandidate  campaign(ELECTION) in the same record: the answer carries the real vote requests.
+ *       won as Candidate     WON. The group leaves the arena's roles: reset(term) as far as the arena holds it
+ *                            (election_elapsed = 0, a fresh draw, votes cleared), then leader_id = self_id, role Follower --
+ *                            which keeps "role != Follower implies leader_id == 0", makes straggling vote responses fall into
+ *                            step_follower's `_ => {}`, and lets a later higher-term record raise RG_GATE_EV_LEADER_CHANGED
+ *                            through the gate: the host's cue to step its leader down. The host raises RG_MF_BECOME_LEADER in
+ *                            its leader engine and stops passing equal-term APPEND / HEARTBEAT records of the group (a correct
+ *                            peer never sends them). A win is not a become_follower: RG_GATE_EV_BECAME_FOLLOWER is not raised.
+ *       lost                 LOST: become_follower(term, 0).
+ *       else                 PENDING.
+ *   vote responses go through the term gate first: m.term > term runs become_follower(m.term, 0) -- STEPPED_DOWN -- except for
+ *     a GRANTED pre-vote response (:1319-1321); m.term < term: IGNORED. Then by role: a Follower does nothing (IGNORED); a
+ *     PreCandidate takes only pre-vote responses, a Candidate only vote responses (else IGNORED). Then poll(from_slot, !reject),
+ *     then maybe_commit_by_vote, literally: after poll, whatever `reject` is, with the role poll left behind -- a group that has
+ *     just won does not commit, one that has just lost does, without the conf check; RG_GATE_EV_CONF_CHECK where a
+ *     still-(pre-)candidate's commit advanced; RG_FOLLOW_HOST where term(m.commit) lies in the gap. The commit info of requests
+ *     a pre-vote win produced is taken BEFORE this commit, as in the reference.
+ *   MsgTimeoutNow takes its header's term / from through the gate (m.term > term: become_follower(m.term, 0); m.term < term:
+ *     IGNORED); then a promotable Follower runs hup(true), a Follower that is not promotable and a (pre-)candidate ignore it --
+ *     IGNORED, or STEPPED_DOWN where the gate changed the term. A TRANSFER campaign's requests carry RG_ELECT_REQ_TRANSFER: the
+ *     host attaches CAMPAIGN_TRANSFER. A plain MsgHup is local: no gate, and no test of `promotable` either (Raft::step has none,
+ *     :1417; the clock filtered its list).
+ * Every call of this section before rg_follow_elect_enable returns RG_ERR_STATE, so does a second enable and one before
+ * rg_follow_gate_enable. rg_checkpoint / rg_restore carry the cells, rg_destroy frees them, rg_device_info.engine_bytes grows
+ * by their size. */
+#define RG_ELECT_CONF_INCOMING(c) ((uint32_t)(c) & 0xffu)
+#define RG_ELECT_CONF_OUTGOING(c) (((uint32_t)(c) >> 8) & 0xffu)
+#define RG_ELECT_CONF_SELF(c) (((uint32_t)(c) >> 16) & 0x7u)
+#define RG_ELECT_CONF_MAKE(incoming, outgoing, self_slot) \
+    (((uint32_t)(incoming) & 0xffu) | (((uint32_t)(outgoing) & 0xffu) << 8) | (((uint32_t)(self_slot) & 0x7u) << 16))
+int rg_follow_elect_enable(rg_engine *h); /* once, after rg_follow_gate_enable: self_id 0, conf 0, no votes */
+typedef struct {
+    uint64_t group, self_id;
+    uint32_t conf;
+    uint8_t yes, no, reserved[2];
+} rg_follow_elect;
+/* Control path; both synchronise. RG_ERR_INVALID_ARG, and nothing written, for a group at or beyond n_follow, self_id == 0, a
+ * slot with both a yes and a no bit, conf bits above bit 18, or two records of one group in the call. A group's self_id has to be
+ * written before its first record. */
+int rg_follow_elect_write(rg_engine *h, const rg_follow_elect *host, uint64_t n);
+int rg_follow_elect_read(rg_engine *h, const uint64_t *host_groups, uint64_t n, rg_follow_elect *host_out);
+typedef struct {
+    uint64_t term; /* the group's term after the record */
+    uint64_t req_term, req_index, req_log_term, req_commit, req_commit_term; /* the vote request (result REQUESTS, else 0) */
+    uint32_t result, events; /* RG_ELECT_*; RG_GATE_EV_* */
+    uint32_t req_kind;       /* RG_FOLLOW_MSG_VOTE / RG_FOLLOW_MSG_PREVOTE, 0 = no requests */
+    uint32_t targets;        /* the slots to send it to */
+    uint32_t status;         /* RG_FOLLOW_NONE, or RG_FOLLOW_HOST: handed back, nothing changed (the dense form: RG_FOLLOW_FAULT) */
+    uint32_t flags;          /* RG_ELECT_REQ_TRANSFER */
+} rg_follow_elect_resp;
+#define RG_ELECT_NONE 0u         /* no record; or status != RG_FOLLOW_NONE */
+#define RG_ELECT_IGNORED 1u      /* nothing changed */
+#define RG_ELECT_BLOCKED 2u      /* hup: pending conf changes */
+#define RG_ELECT_REQUESTS 3u     /* a campaign started: send the requests */
+#define RG_ELECT_PENDING 4u      /* a vote recorded, the election still open */
+#define RG_ELECT_LOST 5u
+#define RG_ELECT_WON 6u
+#define RG_ELECT_STEPPED_DOWN 7u /* the gate's become_follower(m.term, 0) ran and nothing followed */
+#define RG_ELECT_REQ_TRANSFER 0x1u
+/* events: RG_GATE_EV_HARD_STATE (term, vote or commit changed: persist before sending), _BECAME_FOLLOWER (a candidate role
+ * ended in become_follower), _LEADER_CHANGED (leader_id changed: a campaign cleared it, a win set it), _CONF_CHECK. */
+typedef struct {
+    uint8_t *result, *events, *status, *req_kind, *targets, *flags;
+    uint64_t *term, *req_term, *req_index, *req_log_term, *req_commit, *req_commit_term;
+} rg_follow_elect_out;
+/* The storm path: MsgHup for the groups of a DEVICE list, stream-ordered behind whatever wrote it -- rg_follow_clock's dev_hup
+ * with dev_n = rg_follow_clock_counts(h), no host round trip in between. dev_n: a device u64; min(*dev_n, cap) entries are
+ * worked on, the launch is sized by cap. dev_block: u8 [stride] in device memory, != 0 = the group has pending conf changes
+ * (BLOCKED); may be NULL. dev_out: columns in DEVICE memory indexed by LIST POSITION, [cap] each: result, events, status and
+ * term are written for every entry worked on, the other columns where result == RG_ELECT_REQUESTS; nothing beyond
+ * min(*dev_n, cap) is touched. CONTRACT: the list names no group twice (the clock guarantees it); an entry at or beyond
+ * n_follow answers result NONE, status RG_FOLLOW_FAULT. Asynchronous. */
+int rg_follow_campaign_device(rg_engine *h, const uint64_t *dev_groups, const uint64_t *dev_n, uint64_t cap, const uint8_t *dev_block,
+                              const rg_follow_elect_out *dev_out);
+#define RG_CAMPAIGN_TIMEOUT_NOW 0x1u /* a MsgTimeoutNow: through the gate with term / from; else a MsgHup (term / from unused) */
+#define RG_CAMPAIGN_BLOCKED 0x2u     /* the host counted pending conf changes in (applied, committed] */
+typedef struct {
+    uint64_t group, term, from;
+    uint32_t flags, reserved;
+} rg_follow_campaign_req;
+/* Sparse, control path; synchronises. host_resp[i] answers host_reqs[i]. RG_ERR_INVALID_ARG, and nothing applied, for two records
+ * of one group, a group at or beyond n_follow, unknown flags, or a TIMEOUT_NOW record with a term or a from of 0. */
+int rg_follow_campaign(rg_engine *h, const rg_follow_campaign_req *host_reqs, uint64_t n, rg_follow_elect_resp *host_resp);
+typedef struct {
+    uint64_t group, term;        /* Message.term */
+    uint64_t commit, commit_term; /* Message.commit / .commit_term (a reject carries them) */
+    uint8_t from_slot;           /* the slot of Message.from, 0..7 */
+    uint8_t kind;                /* RG_FOLLOW_MSG_VOTE: a MsgRequestVoteResponse; RG_FOLLOW_MSG_PREVOTE: a MsgRequestPreVoteResponse */
+    uint8_t reject, reserved[5];
+} rg_follow_vote_rec;
+/* Sparse: n response records, any groups, several per group allowed -- applied per group in array order (staged as
+ * rg_follow_step_gated stages its records: a stable sort by group, then runs); host_resp[i] answers host_recs[i].
+ * RG_ERR_INVALID_ARG, and nothing applied, for a group at or beyond n_follow, a slot above 7, a kind that is not exactly one of
+ * the two, or a term of 0. Synchronises. */
+int rg_follow_vote_resps(rg_engine *h, const rg_follow_vote_rec *host_recs, uint64_t n, rg_follow_elect_resp *host_resp);
+/* Dense: at most one response per followed group, columns [rg_follow_stride] in DEVICE memory; kind[g] == 0 = no message.
+ * dev_out (indexed by group): result, events and status are written for every group, term where there was a message, the
+ * other columns where result == RG_ELECT_REQUESTS. A malformed cell (a kind that is not one of the two, a slot above 7, a term
+ * of 0) answers result NONE with status RG_FOLLOW_FAULT and changes nothing. Asynchronous. */
+typedef struct {
+    const uint8_t *kind, *slot, *reject;
+    const uint64_t *term, *commit, *commit_term;
+} rg_follow_vote_cols;
+int rg_follow_vote_resps_device(rg_engine *h, const rg_follow_vote_cols *dev_msgs, const rg_follow_elect_out *dev_out);
 
 /* ---- message-at-a-time host mirror of RawNode::step for MsgAppendResponse
  *      (src/raw_node.rs:402-411 -> src/raft.rs:1280-1411 term gate -> :2096-2098) ---- */

@@ -58,6 +58,8 @@ void rg_follow_free(rg_engine *h) {
     if (fo->ckpt) (void)hipFree(fo->ckpt);
     if (fo->soft_arena) (void)hipFree(fo->soft_arena);
     if (fo->soft_ckpt) (void)hipFree(fo->soft_ckpt);
+    if (fo->elect_arena) (void)hipFree(fo->elect_arena);
+    if (fo->elect_ckpt) (void)hipFree(fo->elect_ckpt);
     delete fo;
     h->fo = nullptr;
 }
@@ -71,6 +73,10 @@ int rg_follow_checkpoint(rg_engine *h) {
         if (!fo->soft_ckpt) RG_HIP(hipMalloc(&fo->soft_ckpt, fo->soft_bytes));
         RG_HIP(hipMemcpyAsync(fo->soft_ckpt, fo->soft_arena, fo->soft_bytes, hipMemcpyDeviceToDevice, h->stream));
     }
+    if (fo->elect_arena) { // (the candidate half, abi_elect.hip)
+        if (!fo->elect_ckpt) RG_HIP(hipMalloc(&fo->elect_ckpt, fo->elect_bytes));
+        RG_HIP(hipMemcpyAsync(fo->elect_ckpt, fo->elect_arena, fo->elect_bytes, hipMemcpyDeviceToDevice, h->stream));
+    }
     return RG_OK;
 }
 
@@ -79,6 +85,7 @@ int rg_follow_restore(rg_engine *h) {
     if (!fo || !fo->ckpt) return RG_OK;
     RG_HIP(hipMemcpyAsync(fo->arena, fo->ckpt, fo->bytes, hipMemcpyDeviceToDevice, h->stream));
     if (fo->soft_ckpt) RG_HIP(hipMemcpyAsync(fo->soft_arena, fo->soft_ckpt, fo->soft_bytes, hipMemcpyDeviceToDevice, h->stream));
+    if (fo->elect_ckpt) RG_HIP(hipMemcpyAsync(fo->elect_arena, fo->elect_ckpt, fo->elect_bytes, hipMemcpyDeviceToDevice, h->stream));
     return RG_OK;
 }
 

@@ -27,6 +27,7 @@
 #include "rg_workload.h"
 #include "rg_read.h"
 #include "rg_follow.h"
+#include "rg_elect.h"
 
 #include "rg_tick_kernels.h"
 #include "rg_grow.h"
@@ -128,6 +129,12 @@ struct RgFollowEngine {
     char *soft_arena, *soft_ckpt;
     size_t soft_bytes;               // of the columns
     unsigned long long *clock_counts; // device u64 [2]: groups appended, groups due
+    // the candidate half (rg_follow_elect_enable, abi_elect.hip): the election columns of RgElectCols, [stride] each;
+    // elect_arena == nullptr = off
+    RgElectCols elect;
+    char *elect_arena = nullptr, *elect_ckpt = nullptr;
+    size_t elect_bytes = 0;
+    std::vector<RgElectStaged> elect_recs; // host staging of one sparse batch of records
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -206,7 +206,7 @@ class PublishStats(C.Structure):
                 ("events_on_tick_packets", C.c_uint64)]
 
 
-ABI_VERSION = 10  # RG_ABI_VERSION of include/raftgroups.h these ctypes layouts mirror (tests/test_abi.py compares)
+ABI_VERSION = 11  # RG_ABI_VERSION of include/raftgroups.h these ctypes layouts mirror (tests/test_abi.py compares)
 class CommInfo(C.Structure):
     _fields_ = [("rank", C.c_uint32), ("world", C.c_uint32), ("transport", C.c_uint32), ("in_process", C.c_uint32),
                 ("rccl_ranks", C.c_uint32), ("rccl_rank", C.c_uint32)]
@@ -261,6 +261,26 @@ GATE_FORCE = 1
 GATE_NONE, GATE_PASS, GATE_IGNORED, GATE_STALE_LEADER, GATE_PREVOTE_LOW, GATE_VOTE_GRANT, GATE_VOTE_REJECT = 0, 1, 2, 3, 4, 5, 6
 GATE_EV_HARD_STATE, GATE_EV_BECAME_FOLLOWER, GATE_EV_LEADER_CHANGED, GATE_EV_CONF_CHECK = 1, 2, 4, 8
 ROLE_FOLLOWER, ROLE_PRE_CANDIDATE, ROLE_CANDIDATE = 0, 1, 2
+# ... and the candidate half: campaign, vote responses and poll (rg_follow_elect_enable ...)
+FOLLOW_ELECT_DTYPE = np.dtype([("group", "<u8"), ("self_id", "<u8"), ("conf", "<u4"), ("yes", "u1"), ("no", "u1"), ("reserved", "u1", (2,))])  # rg_follow_elect
+FOLLOW_ELECT_RESP_DTYPE = np.dtype([("term", "<u8"), ("req_term", "<u8"), ("req_index", "<u8"), ("req_log_term", "<u8"), ("req_commit", "<u8"),
+                                    ("req_commit_term", "<u8"), ("result", "<u4"), ("events", "<u4"), ("req_kind", "<u4"), ("targets", "<u4"),
+                                    ("status", "<u4"), ("flags", "<u4")])                           # rg_follow_elect_resp
+FOLLOW_CAMPAIGN_REQ_DTYPE = np.dtype([("group", "<u8"), ("term", "<u8"), ("from", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])  # rg_follow_campaign_req
+FOLLOW_VOTE_REC_DTYPE = np.dtype([("group", "<u8"), ("term", "<u8"), ("commit", "<u8"), ("commit_term", "<u8"), ("from_slot", "u1"), ("kind", "u1"),
+                                  ("reject", "u1"), ("reserved", "u1", (5,))])                       # rg_follow_vote_rec
+assert (FOLLOW_ELECT_DTYPE.itemsize, FOLLOW_ELECT_RESP_DTYPE.itemsize, FOLLOW_CAMPAIGN_REQ_DTYPE.itemsize, FOLLOW_VOTE_REC_DTYPE.itemsize) == (24, 72, 32, 40)
+ELECT_NONE, ELECT_IGNORED, ELECT_BLOCKED, ELECT_REQUESTS, ELECT_PENDING, ELECT_LOST, ELECT_WON, ELECT_STEPPED_DOWN = range(8)
+ELECT_REQ_TRANSFER = 1
+CAMPAIGN_TIMEOUT_NOW, CAMPAIGN_BLOCKED = 1, 2
+ELECT_OUT_COLUMNS = ("result", "events", "status", "req_kind", "targets", "flags", "term", "req_term", "req_index", "req_log_term", "req_commit",
+                     "req_commit_term")  # rg_follow_elect_out: six u8 columns, six u64 columns
+VOTE_COLUMNS = ("kind", "slot", "reject", "term", "commit", "commit_term")  # rg_follow_vote_cols: three u8 columns, three u64 columns
+
+
+def elect_conf_make(incoming, outgoing=0, self_slot=0):
+    """RG_ELECT_CONF_MAKE"""
+    return (incoming & 0xFF) | ((outgoing & 0xFF) << 8) | ((self_slot & 7) << 16)
 
 
 class FollowGateConfig(C.Structure):  # rg_follow_gate_config
@@ -276,6 +296,14 @@ class FollowMsgs(C.Structure):  # rg_follow_msgs: device pointers
 class FollowOut(C.Structure):  # rg_follow_out: device pointers
     _fields_ = [("status", C.c_void_p), ("index", C.c_void_p), ("commit", C.c_void_p), ("conflict", C.c_void_p),
                 ("reject_hint", C.c_void_p), ("log_term", C.c_void_p)]
+
+
+class FollowElectOut(C.Structure):  # rg_follow_elect_out: device pointers
+    _fields_ = [(k, C.c_void_p) for k in ELECT_OUT_COLUMNS]
+
+
+class FollowVoteCols(C.Structure):  # rg_follow_vote_cols: device pointers
+    _fields_ = [(k, C.c_void_p) for k in VOTE_COLUMNS]
 
 
 # every symbol include/raftgroups.h declares: (restype, argtypes)
@@ -363,6 +391,13 @@ SYMBOLS = {
     "rg_follow_step_gated_device": (_i, [_vp, C.POINTER(FollowMsgs), _vp, _vp, C.POINTER(FollowOut), _vp, _vp, _vp]),
     "rg_follow_clock": (_i, [_vp, _vp, _u64, _vp]),
     "rg_follow_clock_counts": (_vp, [_vp]),
+    "rg_follow_elect_enable": (_i, [_vp]),
+    "rg_follow_elect_write": (_i, [_vp, _vp, _u64]),
+    "rg_follow_elect_read": (_i, [_vp, _vp, _u64, _vp]),
+    "rg_follow_campaign_device": (_i, [_vp, _vp, _vp, _u64, _vp, C.POINTER(FollowElectOut)]),
+    "rg_follow_campaign": (_i, [_vp, _vp, _u64, _vp]),
+    "rg_follow_vote_resps": (_i, [_vp, _vp, _u64, _vp]),
+    "rg_follow_vote_resps_device": (_i, [_vp, C.POINTER(FollowVoteCols), C.POINTER(FollowElectOut)]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -1050,6 +1085,58 @@ class Engine:
     def follow_clock_counts(self):
         """Device address of u64 [2]: groups appended, groups due, of the last follow_clock."""
         return self.L.rg_follow_clock_counts(self.h)
+
+    # ---- the candidate half: campaign, vote responses and poll -------------------------------------
+    def follow_elect_enable(self):
+        """rg_follow_elect_enable: the election cells of every followed group. Once, after follow_gate_enable."""
+        self._check(self.L.rg_follow_elect_enable(self.h))
+
+    def follow_elect_write(self, cells):
+        """Load election cells: a FOLLOW_ELECT_DTYPE array (distinct groups, self_id != 0, no slot both yes and no)."""
+        cells = np.ascontiguousarray(cells, dtype=FOLLOW_ELECT_DTYPE)
+        self._check(self.L.rg_follow_elect_write(self.h, cells.ctypes.data, len(cells)))
+
+    def follow_elect_read(self, groups):
+        groups = np.ascontiguousarray(groups, dtype=np.uint64)
+        out = np.zeros(len(groups), dtype=FOLLOW_ELECT_DTYPE)
+        self._check(self.L.rg_follow_elect_read(self.h, groups.ctypes.data, len(groups), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def _dev_ptr(x):
+        return None if x is None else int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+
+    def follow_campaign_device(self, groups, n, cap, out, block=None):
+        """rg_follow_campaign_device (asynchronous): MsgHup for min(*n, cap) groups of the DEVICE list `groups`; n = a device u64
+        (follow_clock_counts()), block = a DEVICE u8 [stride] column or None, out = a dict of DEVICE columns named as
+        ELECT_OUT_COLUMNS, indexed by list position."""
+        p = self._dev_ptr
+        o = FollowElectOut(*[p(out.get(k)) for k in ELECT_OUT_COLUMNS])
+        self._check(self.L.rg_follow_campaign_device(self.h, p(groups), p(n), cap, p(block), C.byref(o)))
+
+    def follow_campaign(self, reqs):
+        """Sparse MsgHup / MsgTimeoutNow records: a FOLLOW_CAMPAIGN_REQ_DTYPE array (distinct groups) -> FOLLOW_ELECT_RESP_DTYPE
+        array, positional."""
+        reqs = np.ascontiguousarray(reqs, dtype=FOLLOW_CAMPAIGN_REQ_DTYPE)
+        resp = np.zeros(len(reqs), dtype=FOLLOW_ELECT_RESP_DTYPE)
+        self._check(self.L.rg_follow_campaign(self.h, reqs.ctypes.data, len(reqs), resp.ctypes.data))
+        return resp
+
+    def follow_vote_resps(self, recs):
+        """Sparse vote responses: a FOLLOW_VOTE_REC_DTYPE array (any groups, array order per group) -> FOLLOW_ELECT_RESP_DTYPE
+        array, positional."""
+        recs = np.ascontiguousarray(recs, dtype=FOLLOW_VOTE_REC_DTYPE)
+        resp = np.zeros(len(recs), dtype=FOLLOW_ELECT_RESP_DTYPE)
+        self._check(self.L.rg_follow_vote_resps(self.h, recs.ctypes.data, len(recs), resp.ctypes.data))
+        return resp
+
+    def follow_vote_resps_device(self, msgs, out):
+        """Dense vote responses (asynchronous): msgs / out are dicts of DEVICE columns named as VOTE_COLUMNS / ELECT_OUT_COLUMNS,
+        [follow_stride()] each, indexed by group."""
+        p = self._dev_ptr
+        m = FollowVoteCols(*[p(msgs.get(k)) for k in VOTE_COLUMNS])
+        o = FollowElectOut(*[p(out.get(k)) for k in ELECT_OUT_COLUMNS])
+        self._check(self.L.rg_follow_vote_resps_device(self.h, C.byref(m), C.byref(o)))
 
     # ---- message-at-a-time mirror of RawNode::step -----------------------------------------------
     def set_peers(self, group, peer_ids, term):
