@@ -5,7 +5,7 @@
 use std::os::raw::{c_char, c_void};
 
 pub const RG_MAX_SLOTS: u32 = 8;
-pub const RG_ABI_VERSION: u32 = 11;
+pub const RG_ABI_VERSION: u32 = 12;
 pub const RG_PF_STATE_MASK: u32 = 0x03;
 pub const RG_STATE_PROBE: u32 = 0;
 pub const RG_STATE_REPLICATE: u32 = 1;
@@ -104,6 +104,12 @@ pub const RG_ELECT_STEPPED_DOWN: u32 = 7;
 pub const RG_ELECT_REQ_TRANSFER: u32 = 0x1;
 pub const RG_CAMPAIGN_TIMEOUT_NOW: u32 = 0x1;
 pub const RG_CAMPAIGN_BLOCKED: u32 = 0x2;
+pub const RG_HANDOFF_NONE: u32 = 0;
+pub const RG_HANDOFF_DONE: u32 = 1;
+pub const RG_HANDOFF_NOT_WON: u32 = 2;
+pub const RG_HANDOFF_CONF: u32 = 3;
+pub const RG_HANDOFF_NOT_PERSISTED: u32 = 4;
+pub const RG_HANDOFF_FAULT: u32 = 5;
 pub const RG_SEND_APPEND: u32 = 1;
 pub const RG_SEND_SNAPSHOT: u32 = 2;
 pub const RG_SEND_HOST: u32 = 3;
@@ -468,6 +474,29 @@ pub struct RgFollowVoteCols {
 }
 
 #[repr(C)]
+pub struct RgHandoffRec {
+    pub follow_group: u64,
+    pub lead_group: u64,
+    pub persisted: u64,
+}
+
+#[repr(C)]
+pub struct RgHandoffResp {
+    pub term: u64,
+    pub last_index: u64,
+    pub commit: u64,
+    pub status: u32,
+    pub out: u32,
+}
+
+#[repr(C)]
+pub struct RgHandoffOut {
+    pub status: *mut u8,
+    pub term: *mut u64,
+    pub last_index: *mut u64,
+}
+
+#[repr(C)]
 pub struct RgAppendResponse {
     pub from: u64,
     pub term: u64,
@@ -710,6 +739,10 @@ extern "C" {
     pub fn rg_follow_campaign(h: *mut RgEngine, host_reqs: *const RgFollowCampaignReq, n: u64, host_resp: *mut RgFollowElectResp) -> i32;
     pub fn rg_follow_vote_resps(h: *mut RgEngine, host_recs: *const RgFollowVoteRec, n: u64, host_resp: *mut RgFollowElectResp) -> i32;
     pub fn rg_follow_vote_resps_device(h: *mut RgEngine, dev_msgs: *const RgFollowVoteCols, dev_out: *const RgFollowElectOut) -> i32;
+    pub fn rg_follow_promote(h: *mut RgEngine, host_recs: *const RgHandoffRec, n: u64, host_resp: *mut RgHandoffResp) -> i32;
+    pub fn rg_follow_promote_device(h: *mut RgEngine, dev_result: *const u8, dev_lead: *const u64, dev_persisted: *const u64, dev_out: *const RgHandoffOut) -> i32;
+    pub fn rg_follow_demote(h: *mut RgEngine, host_recs: *const RgHandoffRec, n: u64, host_resp: *mut RgHandoffResp) -> i32;
+    pub fn rg_follow_demote_device(h: *mut RgEngine, dev_select: *const u8, dev_lead: *const u64, dev_out: *const RgHandoffOut) -> i32;
     pub fn rg_set_peers(h: *mut RgEngine, group: u64, peer_ids: *const u64, n: u32, term: u64) -> i32;
     pub fn rg_step(h: *mut RgEngine, group: u64, m: *const RgAppendResponse) -> i32;
     pub fn rg_step_heartbeat_response(h: *mut RgEngine, group: u64, from: u64, term: u64, commit: u64, ins_full: u8) -> i32;

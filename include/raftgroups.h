@@ -41,7 +41,7 @@ extern "C" {
  * new members keep the old meaning), so a caller is compiled against the header of the library it loads. RG_ABI_VERSION is bumped
  * whenever a struct layout, an enum value or a signature changes; rg_abi_version() returns what the library was built with --
  * compare the two at start-up (raftgroups.hpp and the Python / Rust bindings do). */
-#define RG_ABI_VERSION 11u
+#define RG_ABI_VERSION 12u
 
 /* ---- status codes; the negative values mirror src/errors.rs:6-50 where one applies ----
  * Every entry point that returns int returns one of these and leaves the text in rg_last_error() (per thread). Nothing unwinds
@@ -951,6 +951,86 @@ typedef struct {
     const uint64_t *term, *commit, *commit_term;
 } rg_follow_vote_cols;
 int rg_follow_vote_resps_device(rg_engine *h, const rg_follow_vote_cols *dev_msgs, const rg_follow_elect_out *dev_out);
+
+/* ---- The hand-off: a followed group that won its election becomes a group of the leader engine, and back
+ *      (Raft::become_leader, src/raft.rs:1151-1202, with Raft::reset, :942-971) ----
+ * The follower arena and the leader columns describe a log with the same table: tail_first / tail_term / run_first[] / run_term[] /
+ * n_old of the arena are RG_COL_TERM_LO / RG_COL_CUR_TERM / RG_COL_RUN_FIRST / RG_COL_RUN_TERM / RG_COL_RUN_COUNT of the leader
+ * engine (RG_FOLLOW_RUNS = RG_TERM_RUNS + 1). These four calls copy that summary between the two on the device, so that an election
+ * goes from the timeout to a leader that ticks without the group's state crossing to the host. They add no persistent state.
+ *
+ * PROMOTION of follow group F (log F, soft.term T) into lead group L. A record is all-or-nothing: every status but DONE leaves
+ * every cell of both sides as it was. Refusals, in this order:
+ *   NOT_WON        role != Follower, or leader_id != self_id, or self_id == 0: not what a win leaves.
+ *   CONF           RG_ELECT_CONF_SELF / _INCOMING / _OUTGOING of the arena's conf word differ from RG_CFG_SELF / _INCOMING /
+ *                  _OUTGOING of RG_COL_CFG[L], or the self slot is not in RG_CFG_PRESENT or not below the engine's slot count. The
+ *                  call never writes the voter sets: membership stays the host's (rg_set_config), and the size classes derived
+ *                  from the column stay valid.
+ *   NOT_PERSISTED  persisted != F.last_index (raft.rs:1170 asserts it).
+ *   FAULT          F.last_index + 1 reaches 2^63, or T is not above the term of F's last entry (dummy_term for an empty log); the
+ *                  dense form also for a lead group at or beyond n_groups.
+ * Then the log import: RG_COL_DUMMY_INDEX / _TERM = F's, RG_COL_COMMIT = F.committed, F's older runs become RG_COL_RUN_FIRST /
+ * _TERM[0..] (unused rows 0) with RG_COL_RUN_COUNT, RG_COL_TERM_LO = the tail's first index, RG_COL_CUR_TERM = the tail's term,
+ * RG_COL_TERM_HI = F.last_index (an empty log: TERM_LO = dummy_index + 1, TERM_HI = dummy_index, CUR_TERM = dummy_term). Then
+ * exactly what an RG_MF_BECOME_LEADER event with m_hint = T does in a tick: the old range is filed as a run (a full table drops its
+ * oldest run and thereby declares a gap); every slot of RG_CFG_PRESENT gets Progress::reset(last_index + 1) -- matched 0, Probe,
+ * flags cleared, pending snapshot / snapshot request 0 --; the own slot gets matched = persisted, next = matched + 1, Replicate,
+ * committed_index = committed and keeps RG_PF_PENDING_CONF; committed_index and commit_group_id of the other slots survive; slots
+ * without a Progress are not touched; the TRANSFEREE bits of the cfg word are cleared; the empty entry is appended (TERM_HI += 1,
+ * TERM_LO = TERM_HI, CUR_TERM = T). The answer is {term = T, last_index = the new TERM_HI, commit, out = RG_OUT_BECAME_LEADER |
+ * RG_OUT_APPENDED}: what the tick would have reported, for the host's bcast_append.
+ *   NOT written: RG_COL_OUT and RG_COL_HOST_HINT (they belong to ticks) and all three layers of the arena -- the group stays
+ *   "Follower with leader_id == self_id", as a win leaves it. ReadIndex queues need nothing: they empty lazily when RG_COL_CUR_TERM
+ *   changes. With commit publication on, the call counts as a reloaded commit column (the next check point publishes a full
+ *   snapshot).
+ *   Both forms return RG_ERR_STATE before rg_follow_elect_enable, and on an engine created with max_inflight > 0: emptying device
+ *   Inflights windows outside a tick is deliberately left out (such a store takes the host route: rg_follow_read, rg_load_column,
+ *   RG_MF_BECOME_LEADER in a tick, whose send stage empties the windows).
+ * DEMOTION refreshes the arena's log summary of follow group F from lead group L, which this store has been leading: F.dummy =
+ * RG_COL_DUMMY_*, committed = RG_COL_COMMIT, last_index = RG_COL_TERM_HI, runs = the table's RG_COL_RUN_COUNT runs plus
+ * (TERM_LO, CUR_TERM) as the tail when TERM_LO <= TERM_HI. The result has to be canonical as rg_follow_write demands (else FAULT,
+ * nothing written). Needs only rg_follow_enable; soft and election cells are not touched (the gate's become_follower does that when
+ * the host steps the higher-term record afterwards), nor are the leader columns; engines with max_inflight > 0 are allowed. The
+ * answer is {term = CUR_TERM, last_index, commit, out = 0}.
+ *   ORDER the host keeps: demote BEFORE passing the deposing record through the gate (rg_follow_step_gated*) -- the step's answer
+ *   is computed against the arena's log.
+ * The SPARSE forms are staged like rg_follow_campaign, synchronise and answer per record. RG_ERR_INVALID_ARG, and nothing applied,
+ * for a follow group at or beyond n_follow, a lead group at or beyond n_groups, or two records naming the same follow group or
+ * the same lead group. On an engine with a host mirror (rg_set_peers) rg_follow_promote also refuses a lead group that has queued
+ * mirror events with RG_ERR_SLOT_BUSY (they belong to the old term), as rg_local_become_leader does, and after a DONE registers T
+ * as the group's term in the mirror's gate: RG_COL_CUR_TERM and the registered term of a group belong together.
+ * The DENSE forms take columns [rg_follow_stride] in DEVICE memory indexed by follow group: promotion selects the groups where
+ * dev_result[g] == RG_ELECT_WON -- dev_result is exactly the `result` column rg_follow_vote_resps_device wrote --, demotion those
+ * where dev_select[g] != 0; the group goes to / comes from lead group dev_lead[g] (read for selected groups only).
+ * dev_persisted may be NULL: the host vouches that persisted == last_index. dev_out: status is written for every group below
+ * n_follow (0 = not selected), term and last_index where the status is DONE. An unselected group costs one byte read and one
+ * byte written. Asynchronous on the engine's stream: a tick queued after the call sees the new leader. CONTRACT: the selected
+ * groups name pairwise different lead groups. On an engine with a host mirror the dense forms return RG_ERR_STATE (the gate's
+ * table lives on the host). */
+typedef struct {
+    uint64_t follow_group, lead_group;
+    uint64_t persisted; /* promotion: RaftLog.persisted; unused by demotion */
+} rg_handoff_rec;
+typedef struct {
+    uint64_t term, last_index, commit;
+    uint32_t status; /* RG_HANDOFF_* */
+    uint32_t out;    /* promotion, DONE: RG_OUT_BECAME_LEADER | RG_OUT_APPENDED; else 0 */
+} rg_handoff_resp;
+#define RG_HANDOFF_NONE 0u
+#define RG_HANDOFF_DONE 1u
+#define RG_HANDOFF_NOT_WON 2u       /* promote: role != Follower, or leader_id != self_id, or self_id == 0 */
+#define RG_HANDOFF_CONF 3u          /* promote: the lead group's RG_COL_CFG disagrees with the arena's conf word */
+#define RG_HANDOFF_NOT_PERSISTED 4u /* promote: persisted != last_index (raft.rs:1170 asserts it) */
+#define RG_HANDOFF_FAULT 5u         /* see above; the dense forms also for a lead group >= n_groups */
+typedef struct {
+    uint8_t *status;
+    uint64_t *term, *last_index;
+} rg_handoff_out;
+int rg_follow_promote(rg_engine *h, const rg_handoff_rec *host_recs, uint64_t n, rg_handoff_resp *host_resp);
+int rg_follow_promote_device(rg_engine *h, const uint8_t *dev_result, const uint64_t *dev_lead, const uint64_t *dev_persisted,
+                             const rg_handoff_out *dev_out);
+int rg_follow_demote(rg_engine *h, const rg_handoff_rec *host_recs, uint64_t n, rg_handoff_resp *host_resp);
+int rg_follow_demote_device(rg_engine *h, const uint8_t *dev_select, const uint64_t *dev_lead, const rg_handoff_out *dev_out);
 
 /* ---- message-at-a-time host mirror of RawNode::step for MsgAppendResponse
  *      (src/raw_node.rs:402-411 -> src/raft.rs:1280-1411 term gate -> :2096-2098) ---- */

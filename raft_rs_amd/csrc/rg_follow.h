@@ -35,6 +35,11 @@ typedef unsigned char u8;
 #else
 #define RG_FOLLOW_HD RG_HD /* (the canonical-form check also runs in the library's host code) */
 #endif
+#if defined(__clang__) /* full unrolling where an array must not be indexed dynamically; g++ (the host twins) needs no hint */
+#define RG_FOLLOW_UNROLL _Pragma("unroll")
+#else
+#define RG_FOLLOW_UNROLL
+#endif
 
 // The arena's columns, F = stride groups each. HOT: what the steady append (on the tail, in the tail's term) reads and writes.
 // COLD: read only off that path, written only when a term changes or a log is cut.
@@ -299,11 +304,20 @@ RG_FOLLOW_HD int rg_follow_state_check(const rg_follow_state &s) {
     if (s.committed > s.last_index || s.committed < s.dummy_index || s.last_index < s.dummy_index) return 3;
     if (s.dummy_index == 0 && s.dummy_term != 0) return 4;
     if ((s.n_runs == 0) != (s.last_index == s.dummy_index)) return 5;
-    for (u32 k = 0; k < s.n_runs; k++) {
-        if (k == 0 ? s.run_first[0] <= s.dummy_index : s.run_first[k] <= s.run_first[k - 1]) return 6;
-        if (k == 0 ? s.run_term[0] < s.dummy_term : s.run_term[k] <= s.run_term[k - 1]) return 7;
+    // (a loop of constant length over constant indices: in a kernel -- the hand-off's demotion -- the state stays in registers)
+    u64 prev_first = s.dummy_index, prev_term = s.dummy_term;
+    int rule = 0; // the first one broken, runs in ascending order
+    RG_FOLLOW_UNROLL
+    for (u32 k = 0; k < RG_FOLLOW_RUNS; k++) {
+        if (k < s.n_runs) {
+            if (!rule && s.run_first[k] <= prev_first) rule = 6;
+            if (!rule && (k == 0 ? s.run_term[0] < prev_term : s.run_term[k] <= prev_term)) rule = 7;
+            prev_first = s.run_first[k];
+            prev_term = s.run_term[k];
+        }
     }
-    if (s.n_runs && s.run_first[s.n_runs - 1] > s.last_index) return 8;
+    if (rule) return rule;
+    if (s.n_runs && prev_first > s.last_index) return 8;
     return 0;
 }
 RG_D void rg_follow_store_state(const RgFollowCols &c, const rg_follow_state &s) {

@@ -206,7 +206,7 @@ class PublishStats(C.Structure):
                 ("events_on_tick_packets", C.c_uint64)]
 
 
-ABI_VERSION = 11  # RG_ABI_VERSION of include/raftgroups.h these ctypes layouts mirror (tests/test_abi.py compares)
+ABI_VERSION = 12  # RG_ABI_VERSION of include/raftgroups.h these ctypes layouts mirror (tests/test_abi.py compares)
 class CommInfo(C.Structure):
     _fields_ = [("rank", C.c_uint32), ("world", C.c_uint32), ("transport", C.c_uint32), ("in_process", C.c_uint32),
                 ("rccl_ranks", C.c_uint32), ("rccl_rank", C.c_uint32)]
@@ -276,6 +276,12 @@ CAMPAIGN_TIMEOUT_NOW, CAMPAIGN_BLOCKED = 1, 2
 ELECT_OUT_COLUMNS = ("result", "events", "status", "req_kind", "targets", "flags", "term", "req_term", "req_index", "req_log_term", "req_commit",
                      "req_commit_term")  # rg_follow_elect_out: six u8 columns, six u64 columns
 VOTE_COLUMNS = ("kind", "slot", "reject", "term", "commit", "commit_term")  # rg_follow_vote_cols: three u8 columns, three u64 columns
+# ... and the hand-off between the arena and the leader columns (rg_follow_promote / rg_follow_demote ...)
+HANDOFF_REC_DTYPE = np.dtype([("follow_group", "<u8"), ("lead_group", "<u8"), ("persisted", "<u8")])                              # rg_handoff_rec
+HANDOFF_RESP_DTYPE = np.dtype([("term", "<u8"), ("last_index", "<u8"), ("commit", "<u8"), ("status", "<u4"), ("out", "<u4")])  # rg_handoff_resp
+assert (HANDOFF_REC_DTYPE.itemsize, HANDOFF_RESP_DTYPE.itemsize) == (24, 32)
+HANDOFF_NONE, HANDOFF_DONE, HANDOFF_NOT_WON, HANDOFF_CONF, HANDOFF_NOT_PERSISTED, HANDOFF_FAULT = range(6)
+HANDOFF_OUT_COLUMNS = ("status", "term", "last_index")  # rg_handoff_out: one u8 column, two u64 columns
 
 
 def elect_conf_make(incoming, outgoing=0, self_slot=0):
@@ -304,6 +310,10 @@ class FollowElectOut(C.Structure):  # rg_follow_elect_out: device pointers
 
 class FollowVoteCols(C.Structure):  # rg_follow_vote_cols: device pointers
     _fields_ = [(k, C.c_void_p) for k in VOTE_COLUMNS]
+
+
+class HandoffOut(C.Structure):  # rg_handoff_out: device pointers
+    _fields_ = [(k, C.c_void_p) for k in HANDOFF_OUT_COLUMNS]
 
 
 # every symbol include/raftgroups.h declares: (restype, argtypes)
@@ -398,6 +408,10 @@ SYMBOLS = {
     "rg_follow_campaign": (_i, [_vp, _vp, _u64, _vp]),
     "rg_follow_vote_resps": (_i, [_vp, _vp, _u64, _vp]),
     "rg_follow_vote_resps_device": (_i, [_vp, C.POINTER(FollowVoteCols), C.POINTER(FollowElectOut)]),
+    "rg_follow_promote": (_i, [_vp, _vp, _u64, _vp]),
+    "rg_follow_promote_device": (_i, [_vp, _vp, _vp, _vp, C.POINTER(HandoffOut)]),
+    "rg_follow_demote": (_i, [_vp, _vp, _u64, _vp]),
+    "rg_follow_demote_device": (_i, [_vp, _vp, _vp, C.POINTER(HandoffOut)]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -1137,6 +1151,38 @@ class Engine:
         m = FollowVoteCols(*[p(msgs.get(k)) for k in VOTE_COLUMNS])
         o = FollowElectOut(*[p(out.get(k)) for k in ELECT_OUT_COLUMNS])
         self._check(self.L.rg_follow_vote_resps_device(self.h, C.byref(m), C.byref(o)))
+
+    # ---- the hand-off between the follower arena and the leader columns ----------------------------
+    def follow_promote(self, recs):
+        """Sparse promotion of followed groups that won their election: a HANDOFF_REC_DTYPE array (distinct follow groups,
+        distinct lead groups) -> HANDOFF_RESP_DTYPE array, positional. Synchronises."""
+        recs = np.ascontiguousarray(recs, dtype=HANDOFF_REC_DTYPE)
+        resp = np.zeros(len(recs), dtype=HANDOFF_RESP_DTYPE)
+        self._check(self.L.rg_follow_promote(self.h, recs.ctypes.data, len(recs), resp.ctypes.data))
+        return resp
+
+    def follow_promote_device(self, result, lead, out, persisted=None):
+        """Dense promotion (asynchronous): result = the DEVICE u8 `result` column follow_vote_resps_device wrote, lead = a DEVICE
+        u64 column of lead groups, persisted = a DEVICE u64 column or None (the host vouches for persisted == last_index), out = a
+        dict of DEVICE columns named as HANDOFF_OUT_COLUMNS; [follow_stride()] each, indexed by follow group."""
+        p = self._dev_ptr
+        o = HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS])
+        self._check(self.L.rg_follow_promote_device(self.h, p(result), p(lead), p(persisted), C.byref(o)))
+
+    def follow_demote(self, recs):
+        """Sparse demotion: the arena's log summary of follow_group is refreshed from lead_group (persisted unused) ->
+        HANDOFF_RESP_DTYPE array, positional. Synchronises."""
+        recs = np.ascontiguousarray(recs, dtype=HANDOFF_REC_DTYPE)
+        resp = np.zeros(len(recs), dtype=HANDOFF_RESP_DTYPE)
+        self._check(self.L.rg_follow_demote(self.h, recs.ctypes.data, len(recs), resp.ctypes.data))
+        return resp
+
+    def follow_demote_device(self, select, lead, out):
+        """Dense demotion (asynchronous): the groups where the DEVICE u8 column `select` is non-zero; lead / out as in
+        follow_promote_device."""
+        p = self._dev_ptr
+        o = HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS])
+        self._check(self.L.rg_follow_demote_device(self.h, p(select), p(lead), C.byref(o)))
 
     # ---- message-at-a-time mirror of RawNode::step -----------------------------------------------
     def set_peers(self, group, peer_ids, term):

@@ -4,12 +4,16 @@ import re
 import subprocess
 import sys
 
-# usage: tools/kernel_resources.py [-DRG_P=5] [-DRG_OPT=6] ...   (default: the P=5 tick kernels)
+# usage: tools/kernel_resources.py [--src=raft_rs_amd/csrc/abi_handoff.hip] [-DRG_P=5] [-DRG_OPT=6] ... [name filter ...]
+#        (default: the P=5 tick kernels; --src: the kernels of another unit)
 SRC = "raft_rs_amd/csrc/tick_inst.hip"
-defs = [a for a in sys.argv[1:] if a.startswith("-")]
-if not any(d.startswith("-DRG_P=") for d in defs):
+for a in sys.argv[1:]:
+    if a.startswith("--src="):
+        SRC = a[len("--src="):]
+defs = [a for a in sys.argv[1:] if a.startswith("-") and not a.startswith("--src=")]
+if SRC.endswith("tick_inst.hip") and not any(d.startswith("-DRG_P=") for d in defs):
     defs.append("-DRG_P=5")
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-c", SRC, "-o", "/dev/null",
+cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-c", SRC, "-o", "/dev/null",
        "-Wno-pass-failed", "-Rpass-analysis=kernel-resource-usage"] + defs
 out = subprocess.run(cmd, stderr=subprocess.PIPE, stdout=subprocess.PIPE, text=True).stderr
 rows, cur = [], None
