@@ -6,7 +6,7 @@
 
 // What both promotions need of the engine; 0 = fine.
 static int rg_handoff_promote_state(rg_engine *h, const char *who) {
-    if (!h->fo || !h->fo->elect_arena) return rg_fail(RG_ERR_STATE, "%s: rg_follow_elect_enable first", who);
+    if (!h->fo || !h->fo->has(RG_FL_ELECT)) return rg_fail(RG_ERR_STATE, "%s: rg_follow_elect_enable first", who);
     if (h->ins_arena)
         return rg_fail(RG_ERR_STATE, "%s: the engine holds device Inflights (max_inflight > 0), whose windows only a tick's send stage empties", who);
     return RG_OK;
@@ -21,7 +21,7 @@ static bool rg_handoff_out_complete(const rg_handoff_out &o) { return o.status &
 
 // The host checks of both sparse forms: groups in range, no follow group and no lead group twice.
 static int rg_handoff_check_recs(rg_engine *h, const char *who, const rg_handoff_rec *recs, u64 n) {
-    std::unordered_map<u64, u64> seen_f, seen_l;
+    RgSeen seen_f, seen_l;
     for (u64 i = 0; i < n; i++) {
         const rg_handoff_rec &q = recs[i];
         if (q.follow_group >= h->fo->cols.n || q.lead_group >= h->G)
@@ -40,28 +40,24 @@ static int rg_handoff_check_recs(rg_engine *h, const char *who, const rg_handoff
 // Stage the records, run one lane per record, fetch the answers. Synchronises: the staging is reused by the next call.
 static int rg_handoff_run_list(rg_engine *h, const char *who, bool promote, const rg_handoff_rec *recs, u64 n, rg_handoff_resp *host_resp) {
     RgFollowEngine *fo = h->fo;
-    const size_t off_resp = rg_align(n * sizeof(rg_handoff_rec));
-    fo->stage.assign(off_resp + n * sizeof(rg_handoff_resp), 0);
+    RgLayout lay;
+    lay.add(n * sizeof(rg_handoff_rec));
+    const size_t off_resp = lay.add(n * sizeof(rg_handoff_resp));
+    fo->stage.assign(lay.total, 0);
     memcpy(fo->stage.data(), recs, n * sizeof(rg_handoff_rec));
-    int rc = rg_stage_records(h, fo->stage.data(), fo->stage.size());
-    if (rc) return rc;
-    char *d = static_cast<char *>(h->d_recs);
-    const rg_handoff_rec *d_recs = reinterpret_cast<const rg_handoff_rec *>(d);
-    rg_handoff_resp *d_resp = reinterpret_cast<rg_handoff_resp *>(d + off_resp);
-    const dim3 grid(rg_grid(n, 256)), block(256);
-    const bool ix32 = rg_ix32(h->st, h->P);
-    if (promote) {
-        if (ix32) hipLaunchKernelGGL(k_handoff_promote_list<u32>, grid, block, 0, h->stream, h->st, fo->cols, fo->soft, fo->elect, h->P, d_recs, n, d_resp);
-        else hipLaunchKernelGGL(k_handoff_promote_list<u64>, grid, block, 0, h->stream, h->st, fo->cols, fo->soft, fo->elect, h->P, d_recs, n, d_resp);
-    } else {
-        if (ix32) hipLaunchKernelGGL(k_handoff_demote_list<u32>, grid, block, 0, h->stream, h->st, fo->cols, d_recs, n, d_resp);
-        else hipLaunchKernelGGL(k_handoff_demote_list<u64>, grid, block, 0, h->stream, h->st, fo->cols, d_recs, n, d_resp);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "%s: launch failed: %s", who, hipGetErrorString(e));
-    RG_HIP(hipMemcpyAsync(host_resp, d_resp, n * sizeof(rg_handoff_resp), hipMemcpyDeviceToHost, h->stream));
-    RG_HIP(hipStreamSynchronize(h->stream));
-    return RG_OK;
+    return rg_follow_round_trip(h, who, fo->stage.data(), lay.total, [&](char *d) {
+        const rg_handoff_rec *d_recs = reinterpret_cast<const rg_handoff_rec *>(d);
+        rg_handoff_resp *d_resp = reinterpret_cast<rg_handoff_resp *>(d + off_resp);
+        const dim3 grid(rg_grid(n, 256)), block(256);
+        const bool ix32 = rg_ix32(h->st, h->P);
+        if (promote) {
+            if (ix32) hipLaunchKernelGGL(k_handoff_promote_list<u32>, grid, block, 0, h->stream, h->st, fo->cols, fo->soft, fo->elect, h->P, d_recs, n, d_resp);
+            else hipLaunchKernelGGL(k_handoff_promote_list<u64>, grid, block, 0, h->stream, h->st, fo->cols, fo->soft, fo->elect, h->P, d_recs, n, d_resp);
+        } else {
+            if (ix32) hipLaunchKernelGGL(k_handoff_demote_list<u32>, grid, block, 0, h->stream, h->st, fo->cols, d_recs, n, d_resp);
+            else hipLaunchKernelGGL(k_handoff_demote_list<u64>, grid, block, 0, h->stream, h->st, fo->cols, d_recs, n, d_resp);
+        }
+    }, {{host_resp, off_resp, n * sizeof(rg_handoff_resp)}});
 }
 
 extern "C" int rg_follow_promote(rg_engine *h, const rg_handoff_rec *host_recs, uint64_t n, rg_handoff_resp *host_resp) try {
@@ -105,8 +101,7 @@ extern "C" int rg_follow_promote_device(rg_engine *h, const uint8_t *dev_result,
     else
         hipLaunchKernelGGL(k_handoff_promote_dense<u64>, grid, block, 0, h->stream, h->st, fo->cols, fo->soft, fo->elect, h->P, dev_result, dev_lead, dev_persisted,
                            *dev_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "rg_follow_promote_device: launch failed: %s", hipGetErrorString(e));
+    if (int rc = rg_launch_check("rg_follow_promote_device")) return rc;
     rg_handoff_promoted(h);
     return RG_OK;
 } RG_ABI_GUARD
@@ -130,7 +125,5 @@ extern "C" int rg_follow_demote_device(rg_engine *h, const uint8_t *dev_select, 
     const dim3 grid(rg_grid(fo->cols.n, 256)), block(256);
     if (rg_ix32(h->st, h->P)) hipLaunchKernelGGL(k_handoff_demote_dense<u32>, grid, block, 0, h->stream, h->st, fo->cols, dev_select, dev_lead, *dev_out);
     else hipLaunchKernelGGL(k_handoff_demote_dense<u64>, grid, block, 0, h->stream, h->st, fo->cols, dev_select, dev_lead, *dev_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "rg_follow_demote_device: launch failed: %s", hipGetErrorString(e));
-    return RG_OK;
+    return rg_launch_check("rg_follow_demote_device");
 } RG_ABI_GUARD

@@ -8,6 +8,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <initializer_list>
+#include <memory>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -31,6 +34,7 @@
 
 #include "rg_tick_kernels.h"
 #include "rg_grow.h"
+#include "rg_runs.h"
 
 // live engines of this process PER DEVICE: the Infinity Cache is one per device, and a range of ONE engine only stays
 // resident there (k_tick_split) while no other engine's traffic goes through it. Looked at ONCE, by rg_create, when the cache
@@ -115,26 +119,30 @@ struct RgReadEngine {
 };
 
 // The follower half (abi_follow.hip): the optional arena of the groups this store follows -- its own index space, absent until
-// rg_follow_enable; no tick, flush, publication or rg_permute_groups touches it.
+// rg_follow_enable; no tick, flush, publication or rg_permute_groups touches it. It is built in layers, each absent (arena ==
+// nullptr) until its enable call:
+enum {
+    RG_FL_LOG,   // rg_follow_enable: the columns of RgFollowCols, [stride] each
+    RG_FL_SOFT,  // rg_follow_gate_enable (term gate, vote step, election clock): the columns of RgSoftCols, [stride] each, then --
+                 // behind `bytes`, so no checkpoint carries them -- the two count words of rg_follow_clock
+    RG_FL_ELECT, // rg_follow_elect_enable (the candidate half, abi_elect.hip): the columns of RgElectCols, [stride] each
+    RG_FL_COUNT
+};
+struct RgFollowLayer {
+    char *arena = nullptr, *ckpt = nullptr; // the columns; their checkpoint copy (lazy)
+    size_t bytes = 0;                       // of the columns
+};
 struct RgFollowEngine {
-    RgFollowCols cols;
-    char *arena, *ckpt; // the columns of RgFollowCols, [stride] each; the checkpoint copy (lazy)
-    size_t bytes;
-    std::vector<char> stage;             // host staging of one sparse batch / one read
-    std::vector<u32> order;              // ... its records' positions, sorted by group
-    std::vector<rg_follow_state> states; // ... of one rg_follow_write
-    // the term gate, the vote step and the election clock (rg_follow_gate_enable): the soft columns of RgSoftCols, [stride] each,
-    // then the two count words of rg_follow_clock (which no checkpoint carries); soft_arena == nullptr = off
-    RgSoftCols soft;
-    char *soft_arena, *soft_ckpt;
-    size_t soft_bytes;               // of the columns
-    unsigned long long *clock_counts; // device u64 [2]: groups appended, groups due
-    // the candidate half (rg_follow_elect_enable, abi_elect.hip): the election columns of RgElectCols, [stride] each;
-    // elect_arena == nullptr = off
-    RgElectCols elect;
-    char *elect_arena = nullptr, *elect_ckpt = nullptr;
-    size_t elect_bytes = 0;
-    std::vector<RgElectStaged> elect_recs; // host staging of one sparse batch of records
+    RgFollowLayer layer[RG_FL_COUNT];
+    RgFollowCols cols{};
+    RgSoftCols soft{};
+    RgElectCols elect{};
+    unsigned long long *clock_counts = nullptr; // device u64 [2]: groups appended, groups due
+    std::vector<char> stage;                    // host staging of one sparse batch / one read
+    std::vector<u32> order;                     // ... its records' positions, sorted by group
+    std::vector<rg_follow_state> states;        // ... of one rg_follow_write
+    std::vector<RgElectStaged> elect_recs;      // ... of one batch of election records
+    bool has(int l) const { return layer[l].arena != nullptr; }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -287,8 +295,6 @@ struct RgPub {
     rg_publish_stats stats;
 };
 
-static inline size_t rg_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static inline size_t rg_col_elem(int c) {
     if (c == RG_COL_PFLAGS) return 8; // one u64 row per group
     if (c == RG_COL_CFG || c == RG_COL_OUT) return 4;
@@ -350,4 +356,50 @@ int rg_read_restore(rg_engine *h);
 void rg_follow_free(rg_engine *h);
 int rg_follow_checkpoint(rg_engine *h);
 int rg_follow_restore(rg_engine *h);
+// ... one layer of it: `total` bytes (>= `bytes`, the part a checkpoint carries) allocated and cleared on the engine's stream. The
+// caller finishes with rg_follow_layer_drop (its init kernel did not launch) or adds `total` to engine_bytes.
+int rg_follow_layer_alloc(rg_engine *h, const char *who, RgFollowLayer *l, size_t bytes, size_t total);
+void rg_follow_layer_drop(RgFollowLayer *l);
+// ... and the round trip of every sparse call of the follower side, in this order: `bytes` at `src` staged (rg_stage_records),
+// launch(device base of the staging), the launch check under `who`, the D2H copies of `fetch` in the order given (a null
+// destination is skipped), one hipStreamSynchronize -- the staging is reused by the next call.
+struct RgFetch {
+    void *dst;
+    size_t off, bytes; // device offset in the staging
+};
+int rg_follow_round_trip(rg_engine *h, const char *who, const void *src, size_t bytes, const std::function<void(char *)> &launch,
+                         std::initializer_list<RgFetch> fetch = {});
+
+// What follows a kernel launch of the follower side: 0, or the failure "<who>: launch failed: <HIP's text>".
+static inline int rg_launch_check(const char *who) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? RG_OK : rg_fail(RG_ERR_NO_DEVICE, "%s: launch failed: %s", who, hipGetErrorString(e));
+}
+
+// "No group twice" in the walk of a sparse call's records (one walk in array order: range, rule, then this, so of several faults
+// the first record's is reported): ins = seen.emplace(group, i) -> 0, or the failure naming the record that had the group first.
+typedef std::unordered_map<u64, u64> RgSeen;
+static inline int rg_named_once(const char *who, const std::pair<RgSeen::iterator, bool> &ins, u64 i) {
+    if (ins.second) return RG_OK;
+    return rg_fail(RG_ERR_INVALID_ARG, "%s: records %llu and %llu name group %llu", who, (unsigned long long)ins.first->second, (unsigned long long)i,
+                   (unsigned long long)ins.first->first);
+}
+
+// Groups in, records out (rg_follow_read, rg_follow_soft_read, rg_follow_elect_read): launch(device groups, device records).
+template <typename Rec, typename Launch> static inline int rg_follow_gather(rg_engine *h, const char *who, const u64 *host_groups, u64 n, Rec *host_out, Launch launch) {
+    RgFollowEngine *fo = h->fo;
+    for (u64 i = 0; i < n; i++)
+        if (host_groups[i] >= fo->cols.n)
+            return rg_fail(RG_ERR_INVALID_ARG, "%s: group %llu of %llu", who, (unsigned long long)host_groups[i], (unsigned long long)fo->cols.n);
+    if (n == 0) return RG_OK;
+    RG_ENTER(h);
+    RgLayout lay;
+    lay.add(n * 8);
+    const size_t off_out = lay.add(n * sizeof(Rec));
+    fo->stage.assign(lay.total, 0);
+    memcpy(fo->stage.data(), host_groups, n * 8);
+    return rg_follow_round_trip(h, who, fo->stage.data(), fo->stage.size(),
+                                [&](char *d) { launch(reinterpret_cast<const u64 *>(d), reinterpret_cast<Rec *>(d + off_out)); },
+                                {{host_out, off_out, n * sizeof(Rec)}});
+}
 

@@ -1035,14 +1035,17 @@ class Engine:
         self._check(self.L.rg_follow_step(self.h, msgs.ctypes.data, len(msgs), ext.ctypes.data if n_ext else None, n_ext, resp.ctypes.data))
         return resp
 
+    def _follow_msgs(self, msgs):
+        return FollowMsgs(*[self._dev_ptr(msgs.get(k)) for k in ("flags", "index", "log_term", "commit", "ent_term", "n_entries", "ext", "ext_runs")],
+                          int(msgs.get("n_ext", 0)))
+
+    def _follow_out(self, out):
+        return FollowOut(*[self._dev_ptr(out.get(k)) for k in ("status", "index", "commit", "conflict", "reject_hint", "log_term")])
+
     def follow_step_device(self, msgs, out):
         """Dense step (asynchronous): msgs / out are dicts of DEVICE pointers (ints or objects with data_ptr()) named as the
         fields of rg_follow_msgs / rg_follow_out; msgs may leave out ext / ext_runs / n_ext."""
-        def p(x):
-            return None if x is None else int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
-        m = FollowMsgs(*[p(msgs.get(k)) for k in ("flags", "index", "log_term", "commit", "ent_term", "n_entries", "ext", "ext_runs")],
-                       int(msgs.get("n_ext", 0)))
-        o = FollowOut(*[p(out.get(k)) for k in ("status", "index", "commit", "conflict", "reject_hint", "log_term")])
+        m, o = self._follow_msgs(msgs), self._follow_out(out)
         self._check(self.L.rg_follow_step_device(self.h, C.byref(m), C.byref(o)))
 
     # ---- the follower's term gate, vote step and election clock ------------------------------------
@@ -1081,19 +1084,15 @@ class Engine:
     def follow_step_gated_device(self, msgs, term, from_, out, gate, events, resp_term):
         """Dense gated step (asynchronous): as follow_step_device, with the DEVICE columns term / from_ (u64) and the outputs
         gate / events (u8) and resp_term (u64)."""
-        def p(x):
-            return None if x is None else int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
-        m = FollowMsgs(*[p(msgs.get(k)) for k in ("flags", "index", "log_term", "commit", "ent_term", "n_entries", "ext", "ext_runs")],
-                       int(msgs.get("n_ext", 0)))
-        o = FollowOut(*[p(out.get(k)) for k in ("status", "index", "commit", "conflict", "reject_hint", "log_term")])
+        p = self._dev_ptr
+        m, o = self._follow_msgs(msgs), self._follow_out(out)
         self._check(self.L.rg_follow_step_gated_device(self.h, C.byref(m), p(term), p(from_), C.byref(o), p(gate), p(events), p(resp_term)))
 
     def follow_clock(self, hup, cap, sync=True):
         """rg_follow_clock: one Raft::tick of every followed group; hup = DEVICE u64 [cap] (None with cap 0). sync: -> the number
         appended; else asynchronous, the counts are the two device words at follow_clock_counts()."""
-        ptr = None if hup is None else int(hup.data_ptr()) if hasattr(hup, "data_ptr") else int(hup)
         n = C.c_uint64(0)
-        self._check(self.L.rg_follow_clock(self.h, ptr, cap, C.byref(n) if sync else None))
+        self._check(self.L.rg_follow_clock(self.h, self._dev_ptr(hup), cap, C.byref(n) if sync else None))
         return n.value if sync else None
 
     def follow_clock_counts(self):
