@@ -84,7 +84,7 @@ extern "C" int rg_permute_groups(rg_engine *h, const uint64_t *host_perm) try {
     if (rc) return rc;
     rc = rg_send_materialize(h); // (the compact list keeps the OLD positions in its `group` field: fetch it before this call)
     if (rc) return rc;
-    char *tmp = nullptr, *itmp = nullptr, *rtmp = nullptr;
+    char *tmp = nullptr, *itmp = nullptr, *rtmp = nullptr, *ltmp = nullptr;
     u64 *d_perm = nullptr;
     u32 *etmp = nullptr;
     hipError_t e = hipMalloc(&tmp, h->state_bytes);
@@ -92,6 +92,7 @@ extern "C" int rg_permute_groups(rg_engine *h, const uint64_t *host_perm) try {
     if (e == hipSuccess && h->ins_arena) e = hipMalloc(&itmp, h->ins_state_bytes);
     if (e == hipSuccess && h->esz) e = hipMalloc(&etmp, (size_t)h->G * h->ins.esz_w * 4);
     if (e == hipSuccess && h->rd) e = hipMalloc(&rtmp, h->rd->bytes);
+    if (e == hipSuccess && h->ld) e = hipMalloc(&ltmp, h->ld->bytes); // (every temporary before anything moves)
     if (e == hipSuccess) e = hipMemcpyAsync(d_perm, host_perm, h->G * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(tmp, h->arena, h->state_bytes, hipMemcpyDeviceToDevice, h->stream); // (padding and all)
     if (e == hipSuccess) {
@@ -144,6 +145,8 @@ extern "C" int rg_permute_groups(rg_engine *h, const uint64_t *host_perm) try {
         if (e == hipSuccess) e = hipMemcpyAsync(rd->arena, rtmp, rd->bytes, hipMemcpyDeviceToDevice, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     }
+    if (e == hipSuccess && h->ld) e = rg_lead_place(h, d_perm, ltmp); // ... and the leader's clock cells
+    if (ltmp) (void)hipFree(ltmp);
     if (rtmp) (void)hipFree(rtmp);
     if (tmp) (void)hipFree(tmp);
     if (itmp) (void)hipFree(itmp);
@@ -186,6 +189,10 @@ extern "C" int rg_permute_groups(rg_engine *h, const uint64_t *host_perm) try {
     if (h->rd && h->rd->ckpt) {
         (void)hipFree(h->rd->ckpt);
         h->rd->ckpt = nullptr;
+    }
+    if (h->ld && h->ld->ckpt) {
+        (void)hipFree(h->ld->ckpt);
+        h->ld->ckpt = nullptr;
     }
     return RG_OK;
 } RG_ABI_GUARD

@@ -184,6 +184,7 @@ extern "C" int rg_create(const rg_config *cfg, rg_engine **out) try {
     h->esz = h->esz_ckpt = nullptr;
     h->rd = nullptr;
     h->fo = nullptr;
+    h->ld = nullptr;
     h->d_recs = nullptr;
     h->d_recs_cap = 0;
     h->mbox = nullptr;
@@ -404,6 +405,7 @@ extern "C" void rg_destroy(rg_engine *h) {
     if (h->esz_ckpt) (void)hipFree(h->esz_ckpt);
     rg_read_free(h);
     rg_follow_free(h);
+    rg_lead_free(h);
     if (h->d_recs) (void)hipFree(h->d_recs);
     if (h->msg_arena) (void)hipFree(h->msg_arena);
     if (h->sparse_arena) (void)hipFree(h->sparse_arena);
@@ -519,6 +521,8 @@ extern "C" int rg_checkpoint(rg_engine *h) try {
     }
     const int frc = rg_follow_checkpoint(h); // (the follower arena, if enabled)
     if (frc) return frc;
+    const int lrc = rg_lead_checkpoint(h); // (the leader's clock, if enabled)
+    if (lrc) return lrc;
     return rg_read_checkpoint(h); // (the pending-read queues, if enabled)
 } RG_ABI_GUARD
 
@@ -547,6 +551,8 @@ extern "C" int rg_restore(rg_engine *h) try {
         RG_HIP(hipMemcpyAsync(h->esz, h->esz_ckpt, (size_t)h->G * h->ins.esz_w * 4, hipMemcpyDeviceToDevice, h->stream));
     const int frc = rg_follow_restore(h);
     if (frc) return frc;
+    const int lrc = rg_lead_restore(h);
+    if (lrc) return lrc;
     return rg_read_restore(h);
 } RG_ABI_GUARD
 

@@ -22,6 +22,7 @@
 
 #pragma GCC visibility push(default)
 #include "../../include/raftgroups.h"
+#include "../../include/raftgroups_lead.h"
 #pragma GCC visibility pop
 
 #include "rg_group.h"
@@ -31,6 +32,7 @@
 #include "rg_read.h"
 #include "rg_follow.h"
 #include "rg_elect.h"
+#include "rg_lead.h"
 
 #include "rg_tick_kernels.h"
 #include "rg_grow.h"
@@ -145,6 +147,21 @@ struct RgFollowEngine {
     bool has(int l) const { return layer[l].arena != nullptr; }
 };
 
+// The leader's clock (ext_lead.hip): the optional per-group cells of the LEADER engine -- absent until rgx_lead_clock_enable --, over
+// the engine's stride; rg_permute_groups moves them with their groups.
+struct RgLeadCols {
+    u64 *tag;  // [stride] the RG_COL_CUR_TERM value the clock cell belongs to
+    u32 *cell; // [stride] heartbeat_elapsed | election_elapsed << 14 | STOPPED << 31 (rg_lead.h)
+    RgLeadCfg cfg;
+};
+struct RgLeadEngine {
+    RgLeadCols cols{};
+    char *arena = nullptr, *ckpt = nullptr; // tag | cell, then -- behind `bytes`, so no checkpoint carries them -- the four count words
+    size_t bytes = 0;
+    unsigned long long *counts = nullptr;   // device u64 [4]: beats, check-quorum runs, step-downs, transfers aborted
+    std::vector<char> stage;                // host staging of one write / read
+};
+
 // ------------------------------------------------------------------------------------------------
 // engine object
 // ------------------------------------------------------------------------------------------------
@@ -197,6 +214,7 @@ struct rg_engine {
     u32 *esz, *esz_ckpt; // entry sizes for RG_SEND_BYTES (rg_log_sizes_enable), u32 [G][esz_w]; checkpoint copy (lazy)
     struct RgReadEngine *rd; // ReadIndex: pending-read queues and the list of read states (rg_read_index_enable), nullptr = off
     struct RgFollowEngine *fo; // the follower half: the followed groups' log summaries (rg_follow_enable), nullptr = off
+    struct RgLeadEngine *ld;   // the leader's clock (rgx_lead_clock_enable), nullptr = off
     void *d_recs;      // staging for rg_log_sizes_write / rg_update_state / rg_read_index / rg_follow_* records
     size_t d_recs_cap;
     // resident small-batch path (rg_mailbox_start): request / answer block in pinned host memory, whether the feature is
@@ -356,6 +374,12 @@ int rg_read_restore(rg_engine *h);
 void rg_follow_free(rg_engine *h);
 int rg_follow_checkpoint(rg_engine *h);
 int rg_follow_restore(rg_engine *h);
+// ext_lead.hip: the same for the optional leader clock; rg_lead_place moves the cells with their groups (rg_permute_groups: d_perm
+// is the device copy of the permutation, tmp a device buffer of ld->bytes the caller allocated before anything moved)
+void rg_lead_free(rg_engine *h);
+int rg_lead_checkpoint(rg_engine *h);
+int rg_lead_restore(rg_engine *h);
+hipError_t rg_lead_place(rg_engine *h, const u64 *d_perm, char *tmp);
 // ... one layer of it: `total` bytes (>= `bytes`, the part a checkpoint carries) allocated and cleared on the engine's stream. The
 // caller finishes with rg_follow_layer_drop (its init kernel did not launch) or adds `total` to engine_bytes.
 int rg_follow_layer_alloc(rg_engine *h, const char *who, RgFollowLayer *l, size_t bytes, size_t total);

@@ -232,25 +232,10 @@ __global__ __launch_bounds__(RG_BLOCK) void k_quorum_active(RgState st, u8 *res)
     const u64 g = (u64)blockIdx.x * RG_BLOCK + threadIdx.x;
     if (g >= st.G) return;
     const u32 cfg = st.cfg[g];
-    const u32 self = RG_CFG_SELF(cfg), present = RG_CFG_PRESENT(cfg);
     u64 pf = st.pflags[g];
-    u32 active = 0;
-#pragma unroll
-    for (int p = 0; p < 8; p++) {
-        if (!((present >> p) & 1u)) continue;
-        const u64 bit = (u64)RG_PF_RECENT_ACTIVE << (8 * p);
-        if ((u32)p == self) {
-            pf |= bit;
-            active |= 1u << p;
-        } else if (pf & bit) {
-            active |= 1u << p;
-            pf &= ~bit;
-        }
-    }
+    const bool active = rg_quorum_active_row(cfg, pf); // (rg_lead.h: the leader's clock runs the same row function)
     st.pflags[g] = pf;
-    // has_quorum: vote_result(|id| set.get(id).map(|_| true)) == Won (tracker.rs:367-372)
-    res[g] = rg_vote_joint(rg_vote_majority(RG_CFG_INCOMING(cfg), active, 0),
-                           rg_vote_majority(RG_CFG_OUTGOING(cfg), active, 0)) == 2u;
+    res[g] = active;
 }
 
 // send_heartbeat's commit = min(pr.matched, raft_log.committed) (src/raft.rs:830-838) for every slot

@@ -282,6 +282,15 @@ HANDOFF_RESP_DTYPE = np.dtype([("term", "<u8"), ("last_index", "<u8"), ("commit"
 assert (HANDOFF_REC_DTYPE.itemsize, HANDOFF_RESP_DTYPE.itemsize) == (24, 32)
 HANDOFF_NONE, HANDOFF_DONE, HANDOFF_NOT_WON, HANDOFF_CONF, HANDOFF_NOT_PERSISTED, HANDOFF_FAULT = range(6)
 HANDOFF_OUT_COLUMNS = ("status", "term", "last_index")  # rg_handoff_out: one u8 column, two u64 columns
+LEAD_VERSION = 1  # RGX_LEAD_VERSION of include/raftgroups_lead.h the leader-clock layouts below mirror
+HANDOFF_NO_LEAD = 0xFFFFFFFFFFFFFFFF  # RG_HANDOFF_NO_LEAD: a dev_lead cell of follow_step_down_device that names no lead group
+# ... and the leader's clock (rgx_lead_clock_enable ...)
+LEAD_CLOCK_CELL_DTYPE = np.dtype([("group", "<u8"), ("term", "<u8"), ("election_elapsed", "<u4"), ("heartbeat_elapsed", "<u4"),
+                                  ("led", "u1"), ("reserved", "u1", (7,))])  # rg_lead_clock_cell
+assert LEAD_CLOCK_CELL_DTYPE.itemsize == 32
+LEAD_CLOCK_START_LED = 0x100
+LEAD_EV_BEAT, LEAD_EV_CHECK_QUORUM, LEAD_EV_STEPPED_DOWN, LEAD_EV_TRANSFER_ABORTED, LEAD_EV_NEW_TERM = 0x1, 0x2, 0x4, 0x8, 0x10
+LEAD_CLOCK_OUT_FIELDS = ("events", "beat", "beat_cap", "down", "down_cap", "hb_commit")  # rg_lead_clock_out
 
 
 def elect_conf_make(incoming, outgoing=0, self_slot=0):
@@ -314,6 +323,14 @@ class FollowVoteCols(C.Structure):  # rg_follow_vote_cols: device pointers
 
 class HandoffOut(C.Structure):  # rg_handoff_out: device pointers
     _fields_ = [(k, C.c_void_p) for k in HANDOFF_OUT_COLUMNS]
+
+
+class LeadClockConfig(C.Structure):  # rg_lead_clock_config
+    _fields_ = [("election_tick", C.c_uint32), ("heartbeat_tick", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LeadClockOut(C.Structure):  # rg_lead_clock_out: device pointers and the two list capacities
+    _fields_ = [(k, C.c_uint64 if k.endswith("_cap") else C.c_void_p) for k in LEAD_CLOCK_OUT_FIELDS]
 
 
 # every symbol include/raftgroups.h declares: (restype, argtypes)
@@ -412,6 +429,14 @@ SYMBOLS = {
     "rg_follow_promote_device": (_i, [_vp, _vp, _vp, _vp, C.POINTER(HandoffOut)]),
     "rg_follow_demote": (_i, [_vp, _vp, _u64, _vp]),
     "rg_follow_demote_device": (_i, [_vp, _vp, _vp, C.POINTER(HandoffOut)]),
+    "rgx_lead_version": (C.c_uint32, []),
+    "rgx_lead_clock_enable": (_i, [_vp, C.POINTER(LeadClockConfig)]),
+    "rgx_lead_clock_write": (_i, [_vp, _vp, _u64]),
+    "rgx_lead_clock_read": (_i, [_vp, _vp, _u64, _vp]),
+    "rgx_lead_clock": (_i, [_vp, C.POINTER(LeadClockOut), _vp]),
+    "rgx_lead_clock_counts": (_vp, [_vp]),
+    "rgx_follow_step_down": (_i, [_vp, _vp, _u64, _vp]),
+    "rgx_follow_step_down_device": (_i, [_vp, _vp, _vp, C.POINTER(HandoffOut)]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -1182,6 +1207,53 @@ class Engine:
         p = self._dev_ptr
         o = HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS])
         self._check(self.L.rg_follow_demote_device(self.h, p(select), p(lead), C.byref(o)))
+
+    # ---- the leader's clock and the step-down ------------------------------------------------------
+    def lead_clock_enable(self, election_tick, heartbeat_tick, flags=0):
+        """rgx_lead_clock_enable: the clock cells of every group of the leader engine. Once. flags: GATE_CHECK_QUORUM |
+        LEAD_CLOCK_START_LED."""
+        cfg = LeadClockConfig(election_tick, heartbeat_tick, flags, 0)
+        self._check(self.L.rgx_lead_clock_enable(self.h, C.byref(cfg)))
+
+    def lead_clock_write(self, cells):
+        """Load clock cells: a LEAD_CLOCK_CELL_DTYPE array (distinct groups, both counters below their timeouts)."""
+        cells = np.ascontiguousarray(cells, dtype=LEAD_CLOCK_CELL_DTYPE)
+        self._check(self.L.rgx_lead_clock_write(self.h, cells.ctypes.data, len(cells)))
+
+    def lead_clock_read(self, groups):
+        groups = np.ascontiguousarray(groups, dtype=np.uint64)
+        out = np.zeros(len(groups), dtype=LEAD_CLOCK_CELL_DTYPE)
+        self._check(self.L.rgx_lead_clock_read(self.h, groups.ctypes.data, len(groups), out.ctypes.data))
+        return out
+
+    def lead_clock(self, events, beat=None, beat_cap=0, down=None, down_cap=0, hb_commit=None, sync=True):
+        """rgx_lead_clock: one Raft::tick of every led group. events = DEVICE u8 [n_groups]; beat / down = DEVICE u64 lists of
+        beat_cap / down_cap places or None; hb_commit = DEVICE u64 [P][stride] or None. sync: -> (beats, check-quorum runs,
+        step-downs, transfers aborted); else asynchronous, the counts are the four device words at lead_clock_counts()."""
+        p = self._dev_ptr
+        o = LeadClockOut(p(events), p(beat), beat_cap, p(down), down_cap, p(hb_commit))
+        counts = (C.c_uint64 * 4)()
+        self._check(self.L.rgx_lead_clock(self.h, C.byref(o), counts if sync else None))
+        return tuple(int(x) for x in counts) if sync else None
+
+    def lead_clock_counts(self):
+        """Device address of u64 [4]: beats, check-quorum runs, step-downs, transfers aborted of the last lead_clock."""
+        return self.L.rgx_lead_clock_counts(self.h)
+
+    def follow_step_down(self, recs):
+        """Sparse step-down: demotion of lead_group into follow_group plus become_follower(term, 0) on its soft cells (persisted
+        unused) -> HANDOFF_RESP_DTYPE array, positional. Synchronises."""
+        recs = np.ascontiguousarray(recs, dtype=HANDOFF_REC_DTYPE)
+        resp = np.zeros(len(recs), dtype=HANDOFF_RESP_DTYPE)
+        self._check(self.L.rgx_follow_step_down(self.h, recs.ctypes.data, len(recs), resp.ctypes.data))
+        return resp
+
+    def follow_step_down_device(self, events, lead, out):
+        """Dense step-down (asynchronous): events = the DEVICE u8 [n_groups] column lead_clock wrote, lead = a DEVICE u64
+        [follow_stride()] column of lead groups by follow group (HANDOFF_NO_LEAD = none), out as in follow_promote_device."""
+        p = self._dev_ptr
+        o = HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS])
+        self._check(self.L.rgx_follow_step_down_device(self.h, p(events), p(lead), C.byref(o)))
 
     # ---- message-at-a-time mirror of RawNode::step -----------------------------------------------
     def set_peers(self, group, peer_ids, term):

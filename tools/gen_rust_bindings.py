@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Generate the Rust FFI binding of include/raftgroups.h.
+"""Generate the Rust FFI bindings of include/raftgroups.h and of its extension header include/raftgroups_lead.h.
 
-    python tools/gen_rust_bindings.py            # writes bindings/raftgroups.rs and the block in INTEGRATION.md
+    python tools/gen_rust_bindings.py            # writes bindings/raftgroups.rs, bindings/raftgroups_lead.rs and the block in INTEGRATION.md
     python tools/gen_rust_bindings.py --check    # exit 1 if either is out of date (tests/test_abi.py runs this)
 
 Everything is derived from the header: `#[repr(C)]` structs, the `extern "C"` block (one declaration per exported
@@ -16,6 +16,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "raftgroups.h")
 OUT_RS = os.path.join(ROOT, "bindings", "raftgroups.rs")
+LEAD_HEADER = os.path.join(ROOT, "include", "raftgroups_lead.h")  # the extension: rgx_* functions, RG_* / RGX_* constants
+LEAD_RS = os.path.join(ROOT, "bindings", "raftgroups_lead.rs")
 DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED: tools/gen_rust_bindings.py -->", "<!-- END GENERATED -->"
 
@@ -74,11 +76,13 @@ def parse_decl(decl, typedefs, as_param):
     return name, rt
 
 
-def parse(src):
+def parse(src, fn_prefix="rg_", known=None):
+    """fn_prefix: the prefix of the header's functions; known: typedefs of a header this one includes (the extension)."""
     src = strip_comments(src)
     consts, structs, funcs, enums = [], [], [], []
     typedefs = {"rg_engine": "RgEngine"}
-    for m in re.finditer(r"^[ \t]*#define[ \t]+(RG_\w+)[ \t]+(\(?-?(?:0x[0-9a-fA-F]+|\d+)(?:u|U|ull|ULL)?\)?)[ \t]*$", src, flags=re.M):
+    typedefs.update(known or {})
+    for m in re.finditer(r"^[ \t]*#define[ \t]+(RGX?_\w+)[ \t]+(\(?-?(?:0x[0-9a-fA-F]+|\d+)(?:u|U|ull|ULL)?\)?)[ \t]*$", src, flags=re.M):
         v = m.group(2).strip("()")
         wide = v.lower().endswith("ull")
         v = re.sub(r"(?i)u?l*$", "", v)
@@ -121,7 +125,7 @@ def parse(src):
     body = re.sub(r"typedef\s+(struct|enum)\s*\{.*?\}\s*\w+\s*;", " ", src, flags=re.S)
     body = re.sub(r"typedef[^;{]*;", " ", body)
     body = re.sub(r"^[ \t]*#.*$", " ", body, flags=re.M)
-    for m in re.finditer(r"([\w \t\*]+?)\b(rg_\w+)\s*\(([^()]*)\)\s*;", body, flags=re.S):
+    for m in re.finditer(r"([\w \t\*]+?)\b(" + fn_prefix + r"\w+)\s*\(([^()]*)\)\s*;", body, flags=re.S):
         ret, name, args = " ".join(m.group(1).split()), m.group(2), " ".join(m.group(3).split())
         params = []
         if args and args != "void":
@@ -183,6 +187,30 @@ def generate():
     return emit(*parse(open(HEADER, encoding="utf-8").read()))
 
 
+def generate_lead():
+    """bindings/raftgroups_lead.rs: the extension header's constants, structs and rgx_* functions, over the core module's types."""
+    core = strip_comments(open(HEADER, encoding="utf-8").read())
+    known = {m.group(2): camel(m.group(2)) for m in re.finditer(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", core, flags=re.S)}
+    consts, _, structs, funcs, _ = parse(open(LEAD_HEADER, encoding="utf-8").read(), fn_prefix="rgx_", known=known)
+    o = ["// GENERATED from include/raftgroups_lead.h by tools/gen_rust_bindings.py -- do not edit.",
+         "// The leader's clock, an extension of raftgroups.rs (same library). tests/test_lead_clock_host.py checks that it names every",
+         "// rgx_* export of libraftgroups.so with the header's arity.",
+         "#![allow(non_camel_case_types, dead_code)]",
+         "use super::raftgroups::*;", ""]
+    for name, v, ty in consts:
+        o.append(f"pub const {name}: {ty} = {v};")
+    o.append("pub const RG_HANDOFF_NO_LEAD: u64 = u64::MAX;")
+    o.append("")
+    for sname, fields in structs:
+        o += ["#[repr(C)]", f"pub struct {camel(sname)} {{"] + [f"    pub {ident(fname)}: {ft}," for fname, ft in fields] + ["}", ""]
+    o.append('extern "C" {')
+    for name, ret, params in funcs:
+        ps = ", ".join(f"{ident(n) if n else '_'}: {t}" for n, t in params)
+        o.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
+    o += ["}", ""]
+    return "\n".join(o)
+
+
 def doc_with_block(doc, rs):
     block = f"{BEGIN}\n```rust\n{rs}```\n{END}"
     if BEGIN in doc and END in doc:
@@ -191,13 +219,15 @@ def doc_with_block(doc, rs):
 
 
 def main():
-    rs = generate()
+    rs, lead_rs = generate(), generate_lead()
     doc = open(DOC, encoding="utf-8").read()
     new_doc = doc_with_block(doc, rs)
     if "--check" in sys.argv:
         stale = []
         if not os.path.exists(OUT_RS) or open(OUT_RS, encoding="utf-8").read() != rs:
             stale.append(OUT_RS)
+        if not os.path.exists(LEAD_RS) or open(LEAD_RS, encoding="utf-8").read() != lead_rs:
+            stale.append(LEAD_RS)
         if new_doc != doc:
             stale.append(DOC)
         if stale:
@@ -206,8 +236,9 @@ def main():
         return 0
     os.makedirs(os.path.dirname(OUT_RS), exist_ok=True)
     open(OUT_RS, "w", encoding="utf-8").write(rs)
+    open(LEAD_RS, "w", encoding="utf-8").write(lead_rs)
     open(DOC, "w", encoding="utf-8").write(new_doc)
-    print(f"wrote {OUT_RS} and the generated block of {DOC}")
+    print(f"wrote {OUT_RS}, {LEAD_RS} and the generated block of {DOC}")
     return 0
 
 
