@@ -30,7 +30,9 @@ uint32_t rgx_lead_version(void); /* RGX_LEAD_VERSION of the build */
  * restart: the column changes, the leadership does not begin) corrects the cells with rgx_lead_clock_write afterwards.
  * Every call of this section before rgx_lead_clock_enable returns RG_ERR_STATE (rgx_lead_clock_counts: NULL), so does a second
  * enable. rg_checkpoint / rg_restore carry the cells, rg_permute_groups moves them with their groups, rg_destroy frees them,
- * rg_device_info.engine_bytes grows by their size. Engines with max_inflight > 0 are allowed. */
+ * rg_device_info.engine_bytes grows by their size. Engines with max_inflight > 0 are allowed. An image taken BEFORE the enable call
+ * does not hold the layer: rg_restore to it leaves the cells alone, and a group whose RG_COL_CUR_TERM went back with the image no
+ * longer equals its tag, so by the rule above the next rgx_lead_clock reports RG_LEAD_EV_NEW_TERM for it and restarts its counters. */
 #define RG_LEAD_CLOCK_START_LED 0x100u /* every group starts as led, both counters 0; else every group starts stopped */
 typedef struct {
     uint32_t election_tick;  /* Config::election_tick, 2..16383 */
@@ -61,9 +63,17 @@ int rgx_lead_clock_read(rg_engine *h, const uint64_t *host_groups, uint64_t n, r
  *   RG_COL_MATCH and RG_COL_COMMIT (and the cfg word) only on a beat with hb_commit.
  *   The lists are conveniences: a group that does not fit is still in `events` and was still ticked; the counts are the totals.
  * What a step-down does NOT do: the Progress cells of the group are not reset (they are without meaning until the next
- * become_leader, which resets them; a demotion leaves the leader columns alone too); ReadIndex queues need nothing; device
- * Inflights are emptied by the next RG_MF_BECOME_LEADER tick as today; the ReadIndex context a bcast_heartbeat attaches stays a
- * separate call over the beat list. A leader deposed by a higher term is the host's to stop (rgx_lead_clock_write, led = 0).
+ * become_leader, which resets them; a demotion leaves the leader columns alone too); device Inflights are emptied by the next
+ * RG_MF_BECOME_LEADER tick as today; the ReadIndex context a bcast_heartbeat attaches stays a separate call over the beat list.
+ * What it DOES to the ReadIndex layer, where rg_read_index_enable has run (before or after the clock's enable): the group's pending
+ * reads are dropped unanswered, as reset's `self.read_only = ReadOnly::new(..)` drops them although the term stays (raft.rs:957).
+ * Once the rgx_lead_clock call that reports STEPPED_DOWN has run, in stream order, every ReadIndex entry point finds that group's
+ * queue empty and emits nothing for it: rg_read_pending_counts and rg_read_last_pending report 0, a late heartbeat ack of the same
+ * term releases nothing, and the whole depth is free for the next leadership. The call stores one word for such a group, into the
+ * queue's term cell (a stamp RG_COL_CUR_TERM does not equal), and the queue's own lazy reset does the rest; the stamp travels with
+ * rg_checkpoint / rg_restore and rg_permute_groups like the rest of the queue, and no other group loads or stores a byte more.
+ * ONLY the device's own step-down is covered: a leader deposed by a higher term is the host's to stop (rgx_lead_clock_write,
+ * led = 0), and it keeps its queue until the host's next change of RG_COL_CUR_TERM empties it.
  * Entry conditions are those of rg_quorum_recently_active. On an engine with a host mirror the cached cfg copy is re-read after a
  * call that may have cleared transferee bits. */
 #define RG_LEAD_EV_BEAT 0x1u             /* MsgBeat: bcast_heartbeat is due (raft.rs:1072-1077, :1959-1962) */

@@ -134,8 +134,9 @@ extern "C" int rgx_lead_clock(rg_engine *h, const rg_lead_clock_out *dev_out, ui
     if (!out.down) out.down_cap = 0;
     RG_HIP(hipMemsetAsync(ld->counts, 0, 32, h->stream));
     const dim3 grid(rg_grid(h->G, 256)), block(256);
-    if (rg_ix32(h->st, h->P)) hipLaunchKernelGGL(k_lead_clock<u32>, grid, block, 0, h->stream, h->st, ld->cols, h->P, out, ld->counts);
-    else hipLaunchKernelGGL(k_lead_clock<u64>, grid, block, 0, h->stream, h->st, ld->cols, h->P, out, ld->counts);
+    u64 *read_qterm = h->rd ? h->rd->cols.qterm : nullptr; // a step-down drops the group's pending reads (looked up per call: either enable order)
+    if (rg_ix32(h->st, h->P)) hipLaunchKernelGGL(k_lead_clock<u32>, grid, block, 0, h->stream, h->st, ld->cols, h->P, out, ld->counts, read_qterm);
+    else hipLaunchKernelGGL(k_lead_clock<u64>, grid, block, 0, h->stream, h->st, ld->cols, h->P, out, ld->counts, read_qterm);
     if (int rc = rg_launch_check("rgx_lead_clock")) return rc;
     bool cfg_written = true; // (an asynchronous call cannot know)
     if (host_counts) {

@@ -1,9 +1,10 @@
 // rg_kernels_lead.h -- kernels of ext_lead.hip: the leader's clock (one lane per group of the leader engine, 256-thread blocks) and
 // the way back into the follower arena (one lane per record or per followed group). A lane issues the loads of a phase before its
 // first store; the cfg word and the flag row are loaded only at an election timeout, the matched cells and the commit index only on
-// a beat with hb_commit. The per-slot columns are addressed with the engine's index width (IX, as in rg_kernels_handoff.h). The
-// lists are compacted as k_follow_clock does it: a ballot per wave, ONE atomic per wave and list. No LDS, plain stores. Included by
-// exactly one abi_*.hip unit.
+// a beat with hb_commit. A lane that steps down stores one word more: the term stamp of its group's ReadIndex queue (read_qterm =
+// RgReadCols::qterm, null without that layer), so that the queue's own lazy reset empties it. The per-slot columns are addressed
+// with the engine's index width (IX, as in rg_kernels_handoff.h). The lists are compacted as k_follow_clock does it: a ballot per
+// wave, ONE atomic per wave and list. No LDS, plain stores. Included by exactly one abi_*.hip unit.
 #pragma once
 #include "rg_engine.h"
 #include "rg_kernels_handoff.h"
@@ -30,7 +31,7 @@ RG_D void rg_lead_append(bool mine, u64 g, u64 *list, u64 cap, unsigned long lon
 }
 
 template <typename IX>
-__global__ __launch_bounds__(256) void k_lead_clock(RgState st, RgLeadCols lc, u32 P, rg_lead_clock_out out, unsigned long long *counts) {
+__global__ __launch_bounds__(256) void k_lead_clock(RgState st, RgLeadCols lc, u32 P, rg_lead_clock_out out, unsigned long long *counts, u64 *read_qterm) {
     const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
     u32 ev = 0;
     if (g < st.G) {
@@ -59,6 +60,7 @@ __global__ __launch_bounds__(256) void k_lead_clock(RgState st, RgLeadCols lc, u
         if (a.cell != cell0) lc.cell[g] = a.cell;
         if (cfg != cfg0) st.cfg[g] = cfg;
         if (pf != pf0) st.pflags[g] = pf;
+        if (read_qterm && (ev & RG_LEAD_EV_STEPPED_DOWN)) read_qterm[g] = rg_lead_read_stamp(term); // reset's ReadOnly::new (raft.rs:957)
         if (commits && (ev & RG_LEAD_EV_BEAT)) {
 #pragma unroll
             for (u32 p = 0; p < 8; p++)

@@ -117,6 +117,14 @@ RG_D void rg_lead_beat(RgLeadAdvance &a) {
     if (a.at_heartbeat && !(a.events & RG_LEAD_EV_STEPPED_DOWN)) a.events |= RG_LEAD_EV_BEAT;
 }
 
+// The step-down's `self.read_only = ReadOnly::new(..)` (Raft::reset, raft.rs:957) at the UNCHANGED term: the stamp the group's
+// ReadIndex queue gets in its term cell (RgReadCols::qterm, rg_read.h) in the call that reports STEPPED_DOWN. It differs from
+// cur_term whatever cur_term is, so the queue's own lazy path (rg_read_sync_term) empties it at the next entry point that looks.
+// A LATER term T' > T could hide behind the stamp only if T' == ~T, which needs T < 2^63 <= T': the nearest case is the election
+// from T = 2^63 - 1 to T + 1 = 2^63 == ~T, and no term below 2^63 - 1 has one (log indices end at 2^63 long before a term gets
+// there). Stored only on the step-down path: no other group loads or stores a byte more.
+RG_D u64 rg_lead_read_stamp(u64 cur_term) { return ~cur_term; }
+
 // One Raft::tick of one group: the composition the kernel runs. Returns the events.
 RG_D u32 rg_lead_tick(const RgLeadCfg &lc, u32 &cell, u64 &tag, u64 cur_term, u32 &cfg, u64 &pf) {
     RgLeadAdvance a = rg_lead_advance(lc, cell, tag, cur_term);

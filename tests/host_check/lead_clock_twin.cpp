@@ -8,6 +8,8 @@
 //   W <election_tick> <heartbeat_tick> <election_elapsed> <heartbeat_elapsed> <led> {<reserved>}*7
 //       -> "W <rule>", and for rule 0 " <cell> <election_elapsed> <heartbeat_elapsed> <led>" through rg_lead_cell_of / rg_lead_record
 //   X <cell> <tag> <cur_term>                                            -> "X <cell>"   (rg_lead_stop: the lead group's cell after a step-down)
+//   R <cur_term>                                                         -> "R <stamp> <stamp != cur_term>"   (rg_lead_read_stamp: the term
+//       cell of the group's ReadIndex queue after a step-down)
 //   S <role> <leader_id> <self_id> <term> <clock> <seed> <min> <max> <group>
 //     <commit> <lo> <hi> <cur_term> <dummy> <dummy_term> <run_count> {<first>}*8 {<term>}*8       soft cells; the lead group's log
 //       -> "S <status>", and for DONE " <term> <last_index> <commit> <leader_id> <clock> <stored>" (stored: the cells rg_soft_close
@@ -76,6 +78,9 @@ int main() {
             const u32 cell = (u32)need();
             const u64 tag = need(), cur_term = need();
             printf("X %u\n", rg_lead_stop(cell, tag, cur_term));
+        } else if (kind[0] == 'R') {
+            const u64 cur_term = need(), stamp = rg_lead_read_stamp(cur_term);
+            printf("R %" PRIu64 " %d\n", stamp, stamp != cur_term ? 1 : 0);
         } else if (kind[0] == 'S') {
             RgHandoffWin w;
             w.role = (u32)need();

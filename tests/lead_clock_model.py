@@ -79,17 +79,21 @@ def abort_leader_transfer(g):
     g["cfg"] &= ~(0xF << 20)  # self.lead_transferee = None (raft.rs:2775-2777)
 
 
-def step_down_reset(g):
+def step_down_reset(g, read_only=None):
     """What become_follower(term, INVALID_ID) -> reset(term) (raft.rs:942-971, :1082-1087) does to the cells a leader group has:
-    both counters 0 (:949-950), abort_leader_transfer (:952), and the role (:1086). The Progress reset (:964-970) is left to the
-    next become_leader, which runs it again."""
+    both counters 0 (:949-950), abort_leader_transfer (:952), `self.read_only = ReadOnly::new(..)` (:957) -- the pending reads of
+    `read_only`, a readonly_model.Group, are dropped unanswered although the term stays --, and the role (:1086). The Progress reset
+    (:964-970) is left to the next become_leader, which runs it again."""
     g["el"] = g["hb"] = 0
     abort_leader_transfer(g)
+    if read_only is not None:
+        read_only.reset()  # :957
     g["led"] = False
 
 
-def tick(c, g):
-    """One rgx_lead_clock of one group -> the event byte. The lazy arming, then Raft::tick_heartbeat (raft.rs:1051-1079)."""
+def tick(c, g, read_only=None):
+    """One rgx_lead_clock of one group -> the event byte. The lazy arming, then Raft::tick_heartbeat (raft.rs:1051-1079).
+    read_only: the group's readonly_model.Group where the engine has the ReadIndex layer (a step-down resets it)."""
     ev = 0
     if g["tag"] != g["cur_term"]:  # a new leadership: Raft::reset ran inside become_leader (:1151-1160)
         g["tag"], g["hb"], g["el"], g["led"] = g["cur_term"], 0, 0, True
@@ -103,7 +107,7 @@ def tick(c, g):
         if c.check_quorum:  # :1058-1062 -> step_leader's MsgCheckQuorum arm (:1963-1973)
             ev |= EV_CHECK_QUORUM
             if not quorum_recently_active(g):  # check_quorum_active (:2763-2766)
-                step_down_reset(g)  # become_follower(term, INVALID_ID) (:1969-1970)
+                step_down_reset(g, read_only)  # become_follower(term, INVALID_ID) (:1969-1970)
                 ev |= EV_STEPPED_DOWN
         if g["led"] and g["cfg"] >> 20 & 0xF:  # :1063-1065
             abort_leader_transfer(g)

@@ -7,7 +7,7 @@ not from the engine's:
     src/raft.rs:2056-2091      the MsgReadIndex step of a leader
     src/raft.rs:1805-1818      the read-only half of handle_heartbeat_response
     src/raft.rs:2650-2664      post_conf_change: "the quorum size is now smaller, consider to response some read requests"
-    src/raft.rs:957            Raft::reset: a term change replaces the ReadOnly
+    src/raft.rs:957            Raft::reset: replaces the ReadOnly -- at a term change, and at a step-down at the SAME term
     src/tracker.rs:367-372     has_quorum -> vote_result (src/quorum/majority.rs:130-154, src/quorum/joint.rs:56-67)
 
 Contexts are integers here (the host's handles for the context bytes, 0 = empty), peers are slots, and a group's membership is
@@ -115,7 +115,8 @@ class ReadOnly:
 
 class Group:
     """The leader of one group, as far as reads go. The test owns cfg / commit / term_lo / term and sets them the way its
-    scenario moves the engine's columns; a new term goes through set_term (Raft::reset)."""
+    scenario moves the engine's columns; a new term goes through set_term (Raft::reset), a step-down at the same term through
+    reset (Raft::reset as well)."""
 
     def __init__(self, cfg, commit=0, term_lo=0, term=0, depth=16):
         self.cfg, self.commit, self.term_lo, self.term, self.depth = cfg, commit, term_lo, term, depth
@@ -125,6 +126,12 @@ class Group:
         if term != self.term:
             self.term = term
             self.read_only = ReadOnly()  # raft.rs:957
+
+    def reset(self):
+        """Raft::reset(self.term) at the UNCHANGED term -- become_follower(term, INVALID_ID) of a check-quorum step-down
+        (raft.rs:1963-1972 -> :1082-1087): `self.read_only = ReadOnly::new(self.read_only.option)` (raft.rs:957) runs
+        unconditionally. The queue is empty afterwards and nobody is answered: nothing is emitted."""
+        self.read_only = ReadOnly()  # raft.rs:957
 
     def commit_to_current_term(self):
         return self.commit >= self.term_lo  # raft.rs:581 over the engine's log summary: term(committed) == self.term

@@ -25,9 +25,9 @@ def dev(a):
 class Rig:
     """A leader engine of L.SHAPES[P] x P whose groups are the model's: the edge shapes first, random groups behind them."""
 
-    def __init__(self, rg, P, c, seed, ix64=False, start_led=True, write=True, small=False):
+    def __init__(self, rg, P, c, seed, ix64=False, start_led=True, write=True, small=False, max_inflight=0, before_enable=None):
         self.rg, self.E, self.P, self.c, self.G = rg, rg.engine, P, c, L.SHAPES[P]
-        self.eng = rg.Engine(self.G, P, flags=self.E.CFGF.IX64 if ix64 else None)
+        self.eng = rg.Engine(self.G, P, flags=self.E.CFGF.IX64 if ix64 else None, max_inflight=max_inflight)
         self.stride = self.eng.stride
         rng = random.Random(seed)
         self.groups = [L.random_group(rng, P, c) for _ in range(self.G)]
@@ -46,6 +46,8 @@ class Rig:
         for k in ("cfg", "cur_term", "commit", "pflags", "match"):
             self.eng.load_column(self.E.COL.NAMES.index(k), st[k])
         self.adopt()
+        if before_enable:  # (what a test does between the load and the enable call)
+            before_enable(self)
         self.eng.lead_clock_enable(c.election_tick, c.heartbeat_tick, c.flags | (L.START_LED if start_led else 0))
         if write:
             self.write(range(self.G))

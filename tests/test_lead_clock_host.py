@@ -148,6 +148,32 @@ CONFIG_EDGES = (((2, 1, 0, 0), True), ((1, 1, 0, 0), False), ((2, 2, 0, 0), Fals
                 ((L.TICK_MAX + 1, 1, 0, 0), False), ((10, 3, 2, 0), False), ((10, 3, 1, 1), False), ((10, 9, 0x100, 0), True))
 
 
+def composed_group(rng, depth):
+    """One group of the composed sweep: a led group of lead_clock_model.random_group one increment before its election timeout, and
+    the readonly_model.Group over the same cfg word with 0, 1, depth-1 or depth reads asked for. -> (clock dict, read group,
+    [read states emitted by the requests], [contexts asked for])"""
+    import readonly_model as RO
+    c = L.Config(2, 1, L.CHECK_QUORUM)
+    P = rng.choice((3, 3, 5, 8))
+    g = L.random_group(rng, P, c)
+    g["led"], g["tag"], g["el"], g["hb"] = True, g["cur_term"], c.election_tick - 1, 0
+    ro = RO.Group(g["cfg"], commit=g["commit"], term_lo=0, term=g["cur_term"], depth=depth)
+    asked = [1000 + k for k in range(rng.choice((0, 1, depth - 1, depth)))]
+    emitted = []
+    for ctx in asked:
+        emitted += ro.request(ctx)[1]
+    return c, P, g, ro, emitted, asked
+
+
+def quorum_acks(ro, P, asked):
+    """Every slot answers every context asked for, newest first -- what a quorum of heartbeat responses carries. -> read states"""
+    out = []
+    for ctx in reversed(asked):
+        for s in range(P):
+            out += ro.ack(s, ctx)
+    return out
+
+
 def test_model_cites_the_reference_lines():
     """The model is a restatement with its sources named: tick_heartbeat, the two arms of step_leader, quorum_recently_active with
     has_quorum, send_heartbeat's commit and the reset of a step-down."""
@@ -155,6 +181,70 @@ def test_model_cites_the_reference_lines():
     for cite in ("raft.rs:1051-1079", ":1959-1962", ":1963-1973", "tracker.rs:346-361", ":367-372", "raft.rs:829-839", "raft.rs:942-971", ":1068-1070",
                  ":1063-1065", "src/config.rs:162-171"):
         assert cite in src, cite
+    doc = L.step_down_reset.__doc__
+    assert "(:957)" in doc and "ReadOnly::new" in doc  # the reset of a step-down no longer omits the ReadOnly
+
+
+def test_step_down_reset_takes_a_read_only_group():
+    """step_down_reset(g) alone is what it was; with a readonly_model.Group it empties that group's queue (raft.rs:957) and emits
+    nothing; tick() hands the group through, and resets it in no call but the one that steps down."""
+    import readonly_model as RO
+    cfg3 = L.cfg_word((0, 1, 2), self_slot=0)
+    g = L.new_group(3, cfg3 | 2 << 20, cur_term=5)
+    g["el"], g["hb"] = 3, 1
+    L.step_down_reset(g)
+    assert (g["el"], g["hb"], g["led"], g["cfg"]) == (0, 0, False, cfg3)
+    ro = RO.Group(cfg3, commit=9, term=5, depth=4)
+    assert [ro.request(c)[0] for c in (7, 8)] == [RO.QUEUED] * 2
+    g = L.new_group(3, cfg3, cur_term=5)
+    L.step_down_reset(g, ro)
+    assert ro.queue() == [] and ro.term == 5 and ro.ack(1, 8) == []
+    c = L.Config(3, 1, L.CHECK_QUORUM)
+    g = L.new_group(3, cfg3, cur_term=5)
+    assert ro.request(9)[0] == RO.QUEUED
+    seen = []
+    for _ in range(3):
+        seen.append((L.tick(c, g, ro), len(ro.queue())))
+    assert seen == [(L.EV_BEAT, 1), (L.EV_BEAT, 1), (L.EV_CHECK_QUORUM | L.EV_STEPPED_DOWN, 0)]
+
+
+def test_pending_reads_across_the_step_down_composed():
+    """readonly_model + lead_clock_model over a seeded sweep of 200 groups: reads are queued, the clock ticks to the election
+    timeout, then the acks that would have formed a quorum arrive. A group that stepped down releases NOTHING and reports no pending
+    read; the same acks without the tick -- and on a group that stayed leader -- release exactly the model's states; a read queued
+    after a later set_term(T + 1) is unaffected by the earlier reset."""
+    import copy
+    import readonly_model as RO
+    rng = random.Random(957)
+    kinds = set()
+    for k in range(200):
+        depth = (1, 2, 16)[k % 3]
+        c, P, g, ro, emitted, asked = composed_group(rng, depth)
+        untouched = copy.deepcopy(ro)
+        want = quorum_acks(untouched, P, asked)  # ... without the step-down
+        assert set(want) <= {(ctx, g["commit"]) for ctx in asked} - set(emitted) and len(set(want)) == len(want)
+        pending = len(ro.queue())
+        ev = L.tick(c, g, ro)
+        assert ev & L.EV_CHECK_QUORUM
+        if ev & L.EV_STEPPED_DOWN:
+            assert not g["led"] and ro.queue() == [] and ro.last_pending() == 0 and ro.term == g["cur_term"]
+            assert quorum_acks(ro, P, asked) == [] and ro.ack(0, 0, RO.ACK_LAST_SELF) == []
+        else:
+            assert g["led"] and len(ro.queue()) == pending
+            assert quorum_acks(ro, P, asked) == want
+        kinds.add((bool(ev & L.EV_STEPPED_DOWN), pending == 0, pending == depth, bool(want)))
+        for grp in (ro, untouched):  # the next term: a fresh queue either way, whatever the earlier reset did
+            grp.set_term(g["cur_term"] + 1)
+            grp.term_lo = grp.commit
+            st, rs = grp.request(5000)
+            assert st in (RO.QUEUED, RO.READY) and grp.queue() == ([(5000, grp.commit, 1 << RO.cfg_self(grp.cfg))] if st == RO.QUEUED else [])
+            if st == RO.QUEUED:
+                rs = quorum_acks(grp, P, [5000])
+            assert rs in ([(5000, grp.commit)], [])
+        assert ro.queue() == untouched.queue()
+    for down in (True, False):  # steppers and stayers with empty, partial and full queues, with a releasable quorum
+        assert {(down, True, False, False), (down, False, True, True)} <= kinds, (down, sorted(kinds))
+        assert any(k[0] == down and not k[1] and not k[2] for k in kinds), (down, sorted(kinds))
 
 
 @pytest.mark.parametrize("P", [3, 8])
@@ -244,6 +334,7 @@ def test_sweep_coverage_from_the_model_alone():
     assert [L.Config(*e[:3]).valid(e[3]) for e, _ in CONFIG_EDGES] == [ok for _, ok in CONFIG_EDGES]
 
 
+STAMP_TERMS = (0, 1, 2, 1 << 31, (1 << 32) - 1, (1 << 63) - 1, 1 << 63, (1 << 64) - 2, (1 << 64) - 1)  # RG_COL_CUR_TERM at both ends and in the middle
 STOP_EDGES = ((5 | 3 << 14, 4, 4), (5 | 3 << 14, 3, 4), (1 << 31 | 2, 4, 4), (1 << 31 | 2, 3, 4), (0, 0, 0))  # (cell, tag, RG_COL_CUR_TERM)
 
 
@@ -259,6 +350,13 @@ def run_checks(exe):
         lead.update(cur_term=term, term_lo=1, term_hi=0)
         assert L.step_down(node, lead, g)[0][0] == H.DONE and g["tag"] == term
         assert line.split() == ["X", str(L.cell_word(g))], (line, g)
+    got = subprocess.run([exe], input="".join("R %d\n" % t for t in STAMP_TERMS), stdout=subprocess.PIPE, text=True, check=True).stdout.split("\n")[:-1]
+    assert len(got) == len(STAMP_TERMS)
+    for line, t in zip(got, STAMP_TERMS):  # the ReadIndex queue's term cell after a step-down: never the term (rg_read_sync_term then empties the queue)
+        w = line.split()
+        assert w[0] == "R" and int(w[1]) == ~t & (1 << 64) - 1 != t and int(w[2]) == 1, (line, t)
+        # ... nor the NEXT term, which the queue has to tell from its stamp after an election (the one exception: 2^63 - 1)
+        assert (int(w[1]) == t + 1) == (t == (1 << 63) - 1), (line, t)
     lines = ["W %d %d %d %d %d %s" % (e[0], e[1], e[2], e[3], e[4], " ".join("%d" % x for x in e[5])) for e, _ in WRITE_EDGES]
     lines += ["C %d %d %d %d" % e for e, _ in CONFIG_EDGES]
     got = subprocess.run([exe], input="\n".join(lines) + "\n", stdout=subprocess.PIPE, text=True, check=True).stdout.split("\n")[:-1]

@@ -127,10 +127,10 @@ class ReadChecker:
 class Rig(ReadChecker):
     """An engine with clean leaders (every Progress caught up, Replicate) and the model next to it."""
 
-    def __init__(self, rg, P, depth, seed, n=G, enable=True, cfgs=None):
+    def __init__(self, rg, P, depth, seed, n=G, enable=True, cfgs=None, flags=None):
         self.rg, self.P, self.depth, self.n = rg, P, depth, n
         self.rng = np.random.default_rng(seed)
-        self.eng = eng = rg.Engine(n, P)
+        self.eng = eng = rg.Engine(n, P, flags=flags)
         stride = eng.stride
         self.cfg = mixed_cfgs(self.rng, n, P) if cfgs is None else np.array(cfgs, dtype=np.uint32)
         last = self.rng.integers(5, 50, size=n).astype(np.uint64)

@@ -169,6 +169,34 @@ def test_term_change_drops_pending_reads_and_full_is_loud():
     assert g.queue() == [] and g.ack(1, 6) == []
 
 
+def test_same_term_reset_drops_pending_reads_and_emits_nothing():
+    """Group.reset() is `ReadOnly::new` at the UNCHANGED term (raft.rs:957, reached through become_follower(term, INVALID_ID) of a
+    check-quorum step-down): the queue and the map are empty, last_pending_request_ctx is None, nothing is emitted -- neither by
+    the reset nor by the acks that would have formed a quorum --, the term is what it was, and the whole depth is free again.
+    set_term at the same term, by contrast, is no reset."""
+    src = open(os.path.join(HERE, "readonly_model.py")).read()
+    body = src[src.index("    def reset(self):"):src.index("    def commit_to_current_term")]
+    assert "raft.rs:957" in body and "ReadOnly::new" in body
+    slot, cfg = leader_of([1, 2, 3])
+    for pending in (0, 1, 3, 4):
+        g = M.Group(cfg, commit=4, term_lo=2, term=3, depth=4)
+        ctxs = list(range(10, 10 + pending))
+        assert [g.request(c) for c in ctxs] == [(M.QUEUED, [])] * pending
+        if pending:
+            assert g.ack(slot[1], ctxs[-1]) == []  # (a half-answered queue: the leader's own ack, one short of the quorum)
+        g.set_term(3)
+        assert len(g.queue()) == pending
+        assert g.reset() is None
+        assert g.term == 3 and g.queue() == [] and g.last_pending() == 0 and g.read_only.last_pending_request_ctx() is None
+        assert g.read_only.pending_read_count() == 0 and not g.read_only.pending_read_index
+        for c in ctxs:
+            assert heartbeat_round(g, slot, c, [2, 3]) == []
+        assert g.ack(0, 0, M.ACK_LAST_SELF) == [] and g.queue() == []
+        fresh = list(range(20, 24))
+        assert [g.request(c)[0] for c in fresh + [30]] == [M.QUEUED] * 4 + [M.FULL]
+        assert heartbeat_round(g, slot, fresh[-1], [2]) == [(c, 4) for c in fresh]
+
+
 def test_committed_golden_file_is_what_the_extractor_produces():
     import importlib.util
     if not os.path.isfile("/root/reference/harness/tests/integration_cases/test_raft.rs"):

@@ -10,57 +10,12 @@ import gate_model as G
 import handoff_model as H
 import handoff_rig as R
 import lead_clock_model as L
-from test_follow_elect_gpu import U8_COLS, U64_COLS, cells_array
+from life_cycle_rig import CLOCK, ClockModel, elect_out, expect_arena, node_of, promoted_rig, tick_until_down, vote_round
+from test_follow_elect_gpu import cells_array
 from test_follow_gate_gpu import soft_array, states_array
-from test_handoff_gpu import GATE, OUT_SENT, U64_SENT, Rig, dev
+from test_handoff_gpu import GATE, U64_SENT, Rig, dev
 
 pytestmark = pytest.mark.gpu
-
-CLOCK = L.Config(2, 1, L.CHECK_QUORUM)
-
-
-def promoted_rig(rg, ix64=False):
-    """The 3-slot rig with the model's promotable cases promoted (dense) and the leader's clock enabled behind it: every led group
-    starts at 0 / 0 with the tag of its current term."""
-    rig = Rig(rg, 3, ix64=ix64)
-    cases = H.gpu_cases(3)
-    rig.load_lead(R.state_with(rig.G, 3, rig.eng.stride, cases))
-    rig.load_arena(cases)
-    _, answers = R.model_state(R.state_with(rig.G, 3, rig.eng.stride, cases), cases)
-    rig.promote(cases, True, answers, vouch=True)
-    rig.eng.lead_clock_enable(CLOCK.election_tick, CLOCK.heartbeat_tick, CLOCK.flags | L.START_LED)
-    return rig, cases, [c for c in cases if c.expect == H.DONE]
-
-
-def tick_until_down(rig):
-    """Two clock calls: a promoted group (Progress reset, nobody recent_active but itself) loses its quorum at the first election
-    timeout; the quiet base groups (every peer recent_active) pass their first check. -> the device event column"""
-    import torch
-    events = torch.zeros(rig.eng.stride, dtype=torch.uint8, device="cuda")
-    assert rig.eng.lead_clock(events)[2] == 0
-    counts = rig.eng.lead_clock(events)
-    return events, counts
-
-
-def node_of(g, soft, cells):
-    n = G.Node(GATE, g)
-    n.load(*soft)
-    n.self_id = cells[0]
-    return n
-
-
-def expect_arena(before, lead_state, pairs):
-    """The model's arena after stepping down `pairs` [(follow group, lead group)] -> (arena list, answers)"""
-    want, answers = list(before), []
-    for g, Lg in pairs:
-        canon, soft, cells = before[g]
-        node = node_of(g, soft, cells)
-        a, c = L.step_down(node, R.get_lead(lead_state, Lg))
-        answers.append(a)
-        if a[0] == H.DONE:
-            want[g] = (c, node.soft(), cells)
-    return want, answers
-
 
 @pytest.mark.parametrize("ix64", [False, True])
 def test_step_down_dense_equals_sparse_equals_the_model(rg, ix64):
@@ -133,38 +88,6 @@ def test_refusals_in_order_leave_everything_untouched(rg):
         bare.eng.follow_step_down(recs)
     assert "rg_follow_elect_enable first" in str(ei.value)
     bare.close()
-
-
-class ClockModel:
-    """lead_clock_model over every group of a rig's leader engine: the columns the clock reads are taken from the engine (ticks and
-    promotions write them), the clock cells are the model's own."""
-
-    def __init__(self, rig, c):
-        self.rig, self.c = rig, c
-        self.groups = [L.new_group(rig.P, 0, led=False) for _ in range(rig.G)]
-        self.adopt(first=True)
-
-    def adopt(self, first=False):
-        st = self.rig.read_lead()
-        for i, g in enumerate(self.groups):
-            d = R.get_lead(st, i)
-            g.update(cfg=d["cfg"], cur_term=d["cur_term"], commit=d["commit"], match=d["match"], pflags=d["pflags"] + [0] * (8 - self.rig.P))
-            if first:
-                g["tag"] = g["cur_term"]
-        return st
-
-    def tick(self):
-        return [L.tick(self.c, g) for g in self.groups]
-
-    def check(self, events, want):
-        ev = events.cpu().numpy()
-        assert [int(x) for x in ev[:self.rig.G]] == want, [(i, int(ev[i]), w) for i, w in enumerate(want) if int(ev[i]) != w][:5]
-        got = self.rig.eng.lead_clock_read(np.arange(self.rig.G, dtype=np.uint64))
-        for i, (r, g) in enumerate(zip(got, self.groups)):
-            assert (int(r["term"]), int(r["election_elapsed"]), int(r["heartbeat_elapsed"]), int(r["led"])) == (g["tag"], g["el"], g["hb"], int(g["led"])), (i, r, g)
-        st = self.rig.read_lead()
-        assert [int(x) for x in st["cfg"]] == [g["cfg"] for g in self.groups]
-        assert [[int(b) for b in row[:self.rig.P]] for row in st["pflags"]] == [g["pflags"][:self.rig.P] for g in self.groups]
 
 
 def test_a_device_promotion_arms_the_clock_lazily(rg):
@@ -251,13 +174,7 @@ def test_life_cycle_from_the_election_timeout_to_the_next_one(rg):
     eng.lead_clock_enable(LIFE.election_tick, LIFE.heartbeat_tick, LIFE.flags)  # every group stopped: the promotion arms the winners
     model = ClockModel(r, LIFE)
 
-    def round_cols(kind, term):
-        cols = {k: np.zeros(S, np.uint8) for k in ("kind", "slot", "reject")}
-        cols.update({k: np.zeros(S, np.uint64) for k in ("term", "commit", "commit_term")})
-        for g in winners:
-            cols["kind"][g], cols["slot"][g], cols["term"][g] = kind, 0, term
-        return {k: dev(v) for k, v in cols.items()}
-    pre, real = round_cols(M.PREVOTE, 3), round_cols(M.VOTE, 3)
+    pre, real = vote_round(S, winners, M.PREVOTE, 3), vote_round(S, winners, M.VOTE, 3)
     lead = np.full(S, L.NO_LEAD, np.uint64)
     for g in winners:
         lead[g] = lead_of[g]
@@ -269,10 +186,6 @@ def test_life_cycle_from_the_election_timeout_to_the_next_one(rg):
     keep = [dev(getattr(acks, k)) for k in ("m_index", "m_commit", "m_hint", "m_rs", "m_flags")]
     d_acks = [t.data_ptr() for t in keep]
 
-    def elect_out(size):
-        o = {k: torch.full((size,), OUT_SENT, dtype=torch.uint8, device="cuda") for k in U8_COLS}
-        o.update({k: torch.zeros(size, dtype=torch.int64, device="cuda") for k in U64_COLS})
-        return o
     hup = torch.full((S,), -1, dtype=torch.int64, device="cuda")
     o_camp, o_pre, o_real, o_hand = elect_out(S), elect_out(S), elect_out(S), r.out_columns()
     events = [torch.full((eng.stride,), 0xEE, dtype=torch.uint8, device="cuda") for _ in range(LIFE_TICKS)]
