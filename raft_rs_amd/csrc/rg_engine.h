@@ -23,6 +23,7 @@
 #pragma GCC visibility push(default)
 #include "../../include/raftgroups.h"
 #include "../../include/raftgroups_lead.h"
+#include "../../include/raftgroups_term.h"
 #pragma GCC visibility pop
 
 #include "rg_group.h"
@@ -178,7 +179,8 @@ struct rg_engine {
     char *msg_arena;  // device staging for rg_tick(host msgs) / rg_flush (lazy)
     u64 *zero_col;    // [P][stride] zeros, substituted for NULL m_hint / m_rs
     u64 *rhint;       // [P][stride] reject hints after find_conflict_by_term (pre-pass output)
-    u64 *d_counts;    // scratch for reductions: up to 5 x u64 (rg_msg_stats) of the 256 bytes set aside in rg_create
+    u64 *d_counts;    // scratch for reductions: up to 5 x u64 (rg_msg_stats) of the 256 bytes set aside in rg_create; words 8..10 are the
+                      // counts of the last rgt_lead_gate_device (ext_term.hip), which no reduction clears
     void *d_scratch;  // G x 8 B scratch for host<->device result shuttles
     size_t col_off[RG_COL_COUNT];
     RgState st;

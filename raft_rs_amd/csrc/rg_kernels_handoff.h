@@ -24,6 +24,21 @@ RG_D RgHandoffLog rg_handoff_load_log(const RgFollowCols &c, u64 g) {
     }
     return f;
 }
+// ... and a log summary back into the arena's columns (the demotion, the step-down and the deposition end in it)
+RG_D void rg_handoff_store_log(const RgFollowCols &fc, u64 g, const RgHandoffLog &f) {
+    fc.committed[g] = f.committed;
+    fc.last[g] = f.last;
+    fc.tail_first[g] = f.tail_first;
+    fc.tail_term[g] = f.tail_term;
+    fc.dummy_idx[g] = f.dummy_idx;
+    fc.dummy_term[g] = f.dummy_term;
+    fc.n_old[g] = (u8)f.n_old;
+#pragma unroll
+    for (u32 k = 0; k < RG_TERM_RUNS; k++) {
+        fc.run_first[(u64)k * fc.stride + g] = f.run_first[k];
+        fc.run_term[(u64)k * fc.stride + g] = f.run_term[k];
+    }
+}
 template <typename IX> RG_D RgHandoffLead rg_handoff_load_lead(const RgState &st, IX L) {
     RgHandoffLead l;
     l.commit = rg_at(st.commit, L);
@@ -98,18 +113,7 @@ template <typename IX> RG_D rg_handoff_resp rg_handoff_demote_one(const RgState 
     s.group = g;
     if (rg_handoff_demote(l, s) != RG_HANDOFF_DONE) return rg_handoff_answer(RG_HANDOFF_FAULT, 0, 0, 0, 0);
     const RgHandoffLog f = rg_handoff_export(s);
-    fc.committed[g] = f.committed;
-    fc.last[g] = f.last;
-    fc.tail_first[g] = f.tail_first;
-    fc.tail_term[g] = f.tail_term;
-    fc.dummy_idx[g] = f.dummy_idx;
-    fc.dummy_term[g] = f.dummy_term;
-    fc.n_old[g] = (u8)f.n_old;
-#pragma unroll
-    for (u32 k = 0; k < RG_TERM_RUNS; k++) {
-        fc.run_first[(u64)k * fc.stride + g] = f.run_first[k];
-        fc.run_term[(u64)k * fc.stride + g] = f.run_term[k];
-    }
+    rg_handoff_store_log(fc, g, f);
     return rg_handoff_answer(RG_HANDOFF_DONE, l.cur_term, l.hi, l.commit, 0);
 }
 

@@ -10,12 +10,17 @@
 #include "rg_kernels_handoff.h"
 #include "rg_lead.h"
 
+// rg_kernels_term.h (ext_term.hip) reuses rg_lead_append and rg_lead_step_down_one's pieces: it defines RG_LEAD_KERNELS_SHARED_ONLY, which
+// leaves out the kernels that are not templates (one definition per library: they are ext_lead.hip's).
+#ifndef RG_LEAD_KERNELS_SHARED_ONLY
 __global__ __launch_bounds__(256) void k_lead_init(RgLeadCols lc, const u64 *__restrict__ cur_term, u64 G, u64 stride, u32 led) {
     const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
     if (g >= stride) return;
     lc.tag[g] = g < G ? cur_term[g] : 0;
     lc.cell[g] = g < G && led ? 0u : RG_LEAD_CELL_STOPPED;
 }
+
+#endif
 
 // A wave's lanes with `mine` claim consecutive places of list[cap] with one atomic on *count (which ends as the TRUE total); a lane
 // whose place lies within cap writes its group.
@@ -74,6 +79,7 @@ __global__ __launch_bounds__(256) void k_lead_clock(RgState st, RgLeadCols lc, u
     rg_lead_append((ev & RG_LEAD_EV_TRANSFER_ABORTED) != 0, g, nullptr, 0, &counts[3]);
 }
 
+#ifndef RG_LEAD_KERNELS_SHARED_ONLY
 __global__ __launch_bounds__(256) void k_lead_clock_write(RgLeadCols lc, const rg_lead_clock_cell *__restrict__ recs, u64 n) {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -95,6 +101,8 @@ __global__ __launch_bounds__(256) void k_lead_place(RgLeadCols src, u64 *tag, u3
     tag[i] = src.tag[o];
     cell[i] = src.cell[o];
 }
+
+#endif
 
 // The way back into the arena: lead group L (in range) steps down into follow group g (in range). Nothing is written unless the
 // answer is DONE; `lc` = the clock's columns, lc.cell == nullptr while the clock layer is off. The cell is STOPPED WITH the tag of the
@@ -122,18 +130,7 @@ RG_D rg_handoff_resp rg_lead_step_down_one(const RgState &st, const RgFollowCols
     const RgHandoffLog f = rg_handoff_export(fs);
     rg_lead_step_down_soft(sc.cfg, g, s);
     // ---- stores ----
-    fc.committed[g] = f.committed;
-    fc.last[g] = f.last;
-    fc.tail_first[g] = f.tail_first;
-    fc.tail_term[g] = f.tail_term;
-    fc.dummy_idx[g] = f.dummy_idx;
-    fc.dummy_term[g] = f.dummy_term;
-    fc.n_old[g] = (u8)f.n_old;
-#pragma unroll
-    for (u32 k = 0; k < RG_TERM_RUNS; k++) {
-        fc.run_first[(u64)k * fc.stride + g] = f.run_first[k];
-        fc.run_term[(u64)k * fc.stride + g] = f.run_term[k];
-    }
+    rg_handoff_store_log(fc, g, f);
     rg_soft_close(sc, g, s, so);
     if (lc.cell) {
         const u32 cell = rg_lead_stop(cell0, tag0, l.cur_term);

@@ -291,6 +291,12 @@ assert LEAD_CLOCK_CELL_DTYPE.itemsize == 32
 LEAD_CLOCK_START_LED = 0x100
 LEAD_EV_BEAT, LEAD_EV_CHECK_QUORUM, LEAD_EV_STEPPED_DOWN, LEAD_EV_TRANSFER_ABORTED, LEAD_EV_NEW_TERM = 0x1, 0x2, 0x4, 0x8, 0x10
 LEAD_CLOCK_OUT_FIELDS = ("events", "beat", "beat_cap", "down", "down_cap", "hb_commit")  # rg_lead_clock_out
+# ... and the leader's term gate and the deposition (include/raftgroups_term.h: rgt_lead_gate_device ...)
+TERM_VERSION = 1  # RGT_TERM_VERSION
+TERM_GATE_EV_TRANSFER_ABORTED, TERM_GATE_EV_STALE, TERM_GATE_EV_NOT_LED, TERM_GATE_EV_DEPOSED = 0x08, 0x20, 0x40, 0x80
+TERM_GATE_OUT_FIELDS = ("flags", "events", "new_term", "down", "down_cap")  # rgt_lead_gate_out
+DEPOSE_REC_DTYPE = np.dtype([("follow_group", "<u8"), ("lead_group", "<u8"), ("term", "<u8"), ("reserved", "<u8")])  # rgt_depose_rec
+assert DEPOSE_REC_DTYPE.itemsize == 32
 
 
 def elect_conf_make(incoming, outgoing=0, self_slot=0):
@@ -331,6 +337,10 @@ class LeadClockConfig(C.Structure):  # rg_lead_clock_config
 
 class LeadClockOut(C.Structure):  # rg_lead_clock_out: device pointers and the two list capacities
     _fields_ = [(k, C.c_uint64 if k.endswith("_cap") else C.c_void_p) for k in LEAD_CLOCK_OUT_FIELDS]
+
+
+class TermGateOut(C.Structure):  # rgt_lead_gate_out: device pointers and the list capacity
+    _fields_ = [(k, C.c_uint64 if k.endswith("_cap") else C.c_void_p) for k in TERM_GATE_OUT_FIELDS]
 
 
 # every symbol include/raftgroups.h declares: (restype, argtypes)
@@ -437,6 +447,12 @@ SYMBOLS = {
     "rgx_lead_clock_counts": (_vp, [_vp]),
     "rgx_follow_step_down": (_i, [_vp, _vp, _u64, _vp]),
     "rgx_follow_step_down_device": (_i, [_vp, _vp, _vp, C.POINTER(HandoffOut)]),
+    "rgt_term_version": (C.c_uint32, []),
+    "rgt_lead_gate_device": (_i, [_vp, C.POINTER(_Msgs), _vp, C.POINTER(TermGateOut), _vp]),
+    "rgt_lead_gate_counts": (_vp, [_vp]),
+    "rgt_follow_depose": (_i, [_vp, _vp, _u64, _vp]),
+    "rgt_follow_depose_device": (_i, [_vp, _vp, _vp, _vp, C.POINTER(HandoffOut)]),
+    "rgt_follow_depose_scan_device": (_i, [_vp, _vp, _vp, _vp, C.POINTER(HandoffOut)]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -1254,6 +1270,48 @@ class Engine:
         p = self._dev_ptr
         o = HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS])
         self._check(self.L.rgx_follow_step_down_device(self.h, p(events), p(lead), C.byref(o)))
+
+    # ---- the leader's term gate and the deposition --------------------------------------------------
+    def lead_gate_device(self, m_flags, m_term, events, new_term, flags=None, down=None, down_cap=0, sync=True):
+        """rgt_lead_gate_device: the term check of Raft::step for every record of a dense leader tick, in front of tick_device.
+        m_flags = DEVICE u8 [n_groups][8] (the tick's RG_MF_* rows), m_term = DEVICE u64 [P][stride] (Message.term per record);
+        events = DEVICE u8 [n_groups], new_term = DEVICE u64 [n_groups] (written where DEPOSED), flags = the DEVICE column the
+        filtered rows go to (None: in place, over m_flags), down = DEVICE u64 list of down_cap places or None. sync: -> (groups
+        deposed, stale records dropped, records of not-led groups dropped); else asynchronous, the counts are the three device
+        words at lead_gate_counts()."""
+        p = self._dev_ptr
+        m = _Msgs(None, None, None, None, p(m_flags), None)
+        o = TermGateOut(p(m_flags if flags is None else flags), p(events), p(new_term), p(down), down_cap)
+        counts = (C.c_uint64 * 3)()
+        self._check(self.L.rgt_lead_gate_device(self.h, C.byref(m), p(m_term), C.byref(o), counts if sync else None))
+        return tuple(int(x) for x in counts) if sync else None
+
+    def lead_gate_counts(self):
+        """Device address of u64 [3]: groups deposed, stale records dropped, records of not-led groups dropped by the last gate."""
+        return self.L.rgt_lead_gate_counts(self.h)
+
+    def follow_depose(self, recs):
+        """Sparse deposition: demotion of lead_group into follow_group plus become_follower(term, 0) on its soft cells and the
+        lead-side stop; a DEPOSE_REC_DTYPE array -> HANDOFF_RESP_DTYPE array, positional. Synchronises."""
+        recs = np.ascontiguousarray(recs, dtype=DEPOSE_REC_DTYPE)
+        resp = np.zeros(len(recs), dtype=HANDOFF_RESP_DTYPE)
+        self._check(self.L.rgt_follow_depose(self.h, recs.ctypes.data, len(recs), resp.ctypes.data))
+        return resp
+
+    def follow_depose_device(self, events, new_term, lead, out):
+        """Dense deposition (asynchronous): events / new_term = the DEVICE columns lead_gate_device wrote, lead = a DEVICE u64
+        [follow_stride()] column of lead groups by follow group (HANDOFF_NO_LEAD = none), out as in follow_promote_device."""
+        p = self._dev_ptr
+        o = HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS])
+        self._check(self.L.rgt_follow_depose_device(self.h, p(events), p(new_term), p(lead), C.byref(o)))
+
+    def follow_depose_scan_device(self, msg_flags, term, lead, out):
+        """The deposition by a new leader's record (asynchronous), in front of follow_step_gated_device with that call's own
+        DEVICE columns msg_flags (rg_follow_msgs.flags) and term; lead / out as in follow_depose_device. The soft cells are left
+        to the gated step."""
+        p = self._dev_ptr
+        o = HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS])
+        self._check(self.L.rgt_follow_depose_scan_device(self.h, p(msg_flags), p(term), p(lead), C.byref(o)))
 
     # ---- message-at-a-time mirror of RawNode::step -----------------------------------------------
     def set_peers(self, group, peer_ids, term):

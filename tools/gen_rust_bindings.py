@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Generate the Rust FFI bindings of include/raftgroups.h and of its extension header include/raftgroups_lead.h.
+"""Generate the Rust FFI bindings of include/raftgroups.h and of its extension headers include/raftgroups_lead.h and
+include/raftgroups_term.h.
 
-    python tools/gen_rust_bindings.py            # writes bindings/raftgroups.rs, bindings/raftgroups_lead.rs and the block in INTEGRATION.md
-    python tools/gen_rust_bindings.py --check    # exit 1 if either is out of date (tests/test_abi.py runs this)
+    python tools/gen_rust_bindings.py            # writes bindings/raftgroups.rs, bindings/raftgroups_lead.rs, bindings/raftgroups_term.rs and the block in INTEGRATION.md
+    python tools/gen_rust_bindings.py --check    # exit 1 if any of them is out of date (tests/test_abi.py runs this)
 
 Everything is derived from the header: `#[repr(C)]` structs, the `extern "C"` block (one declaration per exported
 function, same argument order), the numeric constants. No Rust toolchain exists in the build image, so the output is
@@ -18,6 +19,8 @@ HEADER = os.path.join(ROOT, "include", "raftgroups.h")
 OUT_RS = os.path.join(ROOT, "bindings", "raftgroups.rs")
 LEAD_HEADER = os.path.join(ROOT, "include", "raftgroups_lead.h")  # the extension: rgx_* functions, RG_* / RGX_* constants
 LEAD_RS = os.path.join(ROOT, "bindings", "raftgroups_lead.rs")
+TERM_HEADER = os.path.join(ROOT, "include", "raftgroups_term.h")  # the second extension: rgt_* functions and types, RGT_* constants
+TERM_RS = os.path.join(ROOT, "bindings", "raftgroups_term.rs")
 DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED: tools/gen_rust_bindings.py -->", "<!-- END GENERATED -->"
 
@@ -76,13 +79,14 @@ def parse_decl(decl, typedefs, as_param):
     return name, rt
 
 
-def parse(src, fn_prefix="rg_", known=None):
-    """fn_prefix: the prefix of the header's functions; known: typedefs of a header this one includes (the extension)."""
+def parse(src, fn_prefix="rg_", known=None, const_prefix="RGX?_"):
+    """fn_prefix: the prefix of the header's functions; known: typedefs of a header this one includes (the extension);
+    const_prefix: a regular expression for the prefix of the header's constants."""
     src = strip_comments(src)
     consts, structs, funcs, enums = [], [], [], []
     typedefs = {"rg_engine": "RgEngine"}
     typedefs.update(known or {})
-    for m in re.finditer(r"^[ \t]*#define[ \t]+(RGX?_\w+)[ \t]+(\(?-?(?:0x[0-9a-fA-F]+|\d+)(?:u|U|ull|ULL)?\)?)[ \t]*$", src, flags=re.M):
+    for m in re.finditer(r"^[ \t]*#define[ \t]+(" + const_prefix + r"\w+)[ \t]+(\(?-?(?:0x[0-9a-fA-F]+|\d+)(?:u|U|ull|ULL)?\)?)[ \t]*$", src, flags=re.M):
         v = m.group(2).strip("()")
         wide = v.lower().endswith("ull")
         v = re.sub(r"(?i)u?l*$", "", v)
@@ -211,6 +215,36 @@ def generate_lead():
     return "\n".join(o)
 
 
+def struct_names(path):
+    src = strip_comments(open(path, encoding="utf-8").read())
+    return {m.group(2): camel(m.group(2)) for m in re.finditer(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S)}
+
+
+def generate_term():
+    """bindings/raftgroups_term.rs: the second extension header's constants, structs and rgt_* functions, over the types of the
+    core module and of the first extension."""
+    known = struct_names(HEADER)
+    known.update(struct_names(LEAD_HEADER))
+    consts, _, structs, funcs, _ = parse(open(TERM_HEADER, encoding="utf-8").read(), fn_prefix="rgt_", known=known, const_prefix="RGT_")
+    o = ["// GENERATED from include/raftgroups_term.h by tools/gen_rust_bindings.py -- do not edit.",
+         "// The leader's term gate and the deposition, an extension of raftgroups.rs and raftgroups_lead.rs (same library).",
+         "// tests/test_term_gate_host.py checks that it names every rgt_* export of libraftgroups.so with the header's arity.",
+         "#![allow(non_camel_case_types, dead_code)]",
+         "use super::raftgroups::*;",
+         "use super::raftgroups_lead::*;", ""]
+    for name, v, ty in consts:
+        o.append(f"pub const {name}: {ty} = {v};")
+    o.append("")
+    for sname, fields in structs:
+        o += ["#[repr(C)]", f"pub struct {camel(sname)} {{"] + [f"    pub {ident(fname)}: {ft}," for fname, ft in fields] + ["}", ""]
+    o.append('extern "C" {')
+    for name, ret, params in funcs:
+        ps = ", ".join(f"{ident(n) if n else '_'}: {t}" for n, t in params)
+        o.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
+    o += ["}", ""]
+    return "\n".join(o)
+
+
 def doc_with_block(doc, rs):
     block = f"{BEGIN}\n```rust\n{rs}```\n{END}"
     if BEGIN in doc and END in doc:
@@ -219,7 +253,7 @@ def doc_with_block(doc, rs):
 
 
 def main():
-    rs, lead_rs = generate(), generate_lead()
+    rs, lead_rs, term_rs = generate(), generate_lead(), generate_term()
     doc = open(DOC, encoding="utf-8").read()
     new_doc = doc_with_block(doc, rs)
     if "--check" in sys.argv:
@@ -228,6 +262,8 @@ def main():
             stale.append(OUT_RS)
         if not os.path.exists(LEAD_RS) or open(LEAD_RS, encoding="utf-8").read() != lead_rs:
             stale.append(LEAD_RS)
+        if not os.path.exists(TERM_RS) or open(TERM_RS, encoding="utf-8").read() != term_rs:
+            stale.append(TERM_RS)
         if new_doc != doc:
             stale.append(DOC)
         if stale:
@@ -237,8 +273,9 @@ def main():
     os.makedirs(os.path.dirname(OUT_RS), exist_ok=True)
     open(OUT_RS, "w", encoding="utf-8").write(rs)
     open(LEAD_RS, "w", encoding="utf-8").write(lead_rs)
+    open(TERM_RS, "w", encoding="utf-8").write(term_rs)
     open(DOC, "w", encoding="utf-8").write(new_doc)
-    print(f"wrote {OUT_RS}, {LEAD_RS} and the generated block of {DOC}")
+    print(f"wrote {OUT_RS}, {LEAD_RS}, {TERM_RS} and the generated block of {DOC}")
     return 0
 
 
