@@ -180,7 +180,8 @@ struct rg_engine {
     u64 *zero_col;    // [P][stride] zeros, substituted for NULL m_hint / m_rs
     u64 *rhint;       // [P][stride] reject hints after find_conflict_by_term (pre-pass output)
     u64 *d_counts;    // scratch for reductions: up to 5 x u64 (rg_msg_stats) of the 256 bytes set aside in rg_create; words 8..10 are the
-                      // counts of the last rgt_lead_gate_device (ext_term.hip), which no reduction clears
+                      // counts of the last rgt_lead_gate_device (ext_term.hip), words 16..21 those of the last rgv_follow_vote_device and
+                      // its list cursor (ext_vote.hip); no reduction clears either
     void *d_scratch;  // G x 8 B scratch for host<->device result shuttles
     size_t col_off[RG_COL_COUNT];
     RgState st;

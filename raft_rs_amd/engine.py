@@ -297,6 +297,15 @@ TERM_GATE_EV_TRANSFER_ABORTED, TERM_GATE_EV_STALE, TERM_GATE_EV_NOT_LED, TERM_GA
 TERM_GATE_OUT_FIELDS = ("flags", "events", "new_term", "down", "down_cap")  # rgt_lead_gate_out
 DEPOSE_REC_DTYPE = np.dtype([("follow_group", "<u8"), ("lead_group", "<u8"), ("term", "<u8"), ("reserved", "<u8")])  # rgt_depose_rec
 assert DEPOSE_REC_DTYPE.itemsize == 32
+# ... and the dense vote step (include/raftgroups_vote.h: rgv_follow_vote_device ...)
+VOTE_VERSION = 1  # RGV_VOTE_VERSION
+VOTE_EV_LED, VOTE_EV_TRANSFER_ABORTED, VOTE_EV_DEPOSED = 0x20, 0x40, 0x80
+VOTE_OUT_FIELDS = ("status", "gate", "events", "term", "commit", "log_term", "answered", "answered_cap")  # rgv_vote_out
+VOTE_REC_DTYPE = np.dtype([("follow_group", "<u8"), ("lead_group", "<u8"), ("term", "<u8"), ("from", "<u8"), ("index", "<u8"), ("log_term", "<u8"),
+                           ("commit", "<u8"), ("commit_term", "<u8"), ("priority", "<i8"), ("kind", "<u4"), ("flags", "<u4")])  # rgv_vote_rec
+VOTE_RESP_DTYPE = np.dtype([("term", "<u8"), ("commit", "<u8"), ("log_term", "<u8"), ("last_index", "<u8"), ("gate", "<u4"), ("events", "<u4"),
+                            ("status", "<u4"), ("reserved", "<u4")])  # rgv_vote_resp
+assert VOTE_REC_DTYPE.itemsize == 80 and VOTE_RESP_DTYPE.itemsize == 48
 
 
 def elect_conf_make(incoming, outgoing=0, self_slot=0):
@@ -341,6 +350,10 @@ class LeadClockOut(C.Structure):  # rg_lead_clock_out: device pointers and the t
 
 class TermGateOut(C.Structure):  # rgt_lead_gate_out: device pointers and the list capacity
     _fields_ = [(k, C.c_uint64 if k.endswith("_cap") else C.c_void_p) for k in TERM_GATE_OUT_FIELDS]
+
+
+class VoteOut(C.Structure):  # rgv_vote_out: device pointers and the list capacity
+    _fields_ = [(k, C.c_uint64 if k.endswith("_cap") else C.c_void_p) for k in VOTE_OUT_FIELDS]
 
 
 # every symbol include/raftgroups.h declares: (restype, argtypes)
@@ -453,6 +466,10 @@ SYMBOLS = {
     "rgt_follow_depose": (_i, [_vp, _vp, _u64, _vp]),
     "rgt_follow_depose_device": (_i, [_vp, _vp, _vp, _vp, C.POINTER(HandoffOut)]),
     "rgt_follow_depose_scan_device": (_i, [_vp, _vp, _vp, _vp, C.POINTER(HandoffOut)]),
+    "rgv_vote_version": (C.c_uint32, []),
+    "rgv_follow_vote_device": (_i, [_vp, C.POINTER(FollowMsgs), _vp, _vp, _vp, _vp, _vp, C.POINTER(VoteOut), _vp]),
+    "rgv_follow_vote": (_i, [_vp, _vp, _u64, _vp]),
+    "rgv_follow_vote_counts": (_vp, [_vp]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -1312,6 +1329,34 @@ class Engine:
         p = self._dev_ptr
         o = HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS])
         self._check(self.L.rgt_follow_depose_scan_device(self.h, p(msg_flags), p(term), p(lead), C.byref(o)))
+
+    # ---- the dense vote step ------------------------------------------------------------------------
+    def follow_vote_device(self, msgs, term, from_, out, priority=None, hdr_flags=None, lead=None, answered=None, answered_cap=0, sync=True):
+        """rgv_follow_vote_device: MsgRequestVote / MsgRequestPreVote for every followed group in one launch, in front of
+        lead_gate_device. msgs / term / from_ = the DEVICE columns of follow_step_gated_device (a request: the flag byte is exactly
+        FOLLOW_MSG_VOTE or _PREVOTE); priority = DEVICE i64, hdr_flags = DEVICE u8 (GATE_FORCE), lead = the DEVICE u64 map of
+        follow_depose_device, each or None; out = a dict of DEVICE columns status / gate / events (u8) and term / commit / log_term
+        (u64); answered = a DEVICE u64 list of answered_cap places or None. sync: -> (requests, grants, rejects, ignored, deposed);
+        else asynchronous, the counts are the five device words at follow_vote_counts()."""
+        p = self._dev_ptr
+        m = self._follow_msgs(msgs)
+        o = VoteOut(*[p(out.get(k)) for k in VOTE_OUT_FIELDS[:6]], p(answered), answered_cap)
+        counts = (C.c_uint64 * 5)()
+        self._check(self.L.rgv_follow_vote_device(self.h, C.byref(m), p(term), p(from_), p(priority), p(hdr_flags), p(lead), C.byref(o),
+                                                  counts if sync else None))
+        return tuple(int(x) for x in counts) if sync else None
+
+    def follow_vote(self, recs):
+        """Sparse vote step: a VOTE_REC_DTYPE array (lead_group = HANDOFF_NO_LEAD where the store does not lead the group) ->
+        VOTE_RESP_DTYPE array, positional. Synchronises."""
+        recs = np.ascontiguousarray(recs, dtype=VOTE_REC_DTYPE)
+        resp = np.zeros(len(recs), dtype=VOTE_RESP_DTYPE)
+        self._check(self.L.rgv_follow_vote(self.h, recs.ctypes.data, len(recs), resp.ctypes.data))
+        return resp
+
+    def follow_vote_counts(self):
+        """Device address of u64 [5]: requests, grants, rejects, ignored, deposed of the last follow_vote_device."""
+        return self.L.rgv_follow_vote_counts(self.h)
 
     # ---- message-at-a-time mirror of RawNode::step -----------------------------------------------
     def set_peers(self, group, peer_ids, term):

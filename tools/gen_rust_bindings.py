@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Generate the Rust FFI bindings of include/raftgroups.h and of its extension headers include/raftgroups_lead.h and
-include/raftgroups_term.h.
+"""Generate the Rust FFI bindings of include/raftgroups.h and of its extension headers include/raftgroups_lead.h,
+include/raftgroups_term.h and include/raftgroups_vote.h.
 
-    python tools/gen_rust_bindings.py            # writes bindings/raftgroups.rs, bindings/raftgroups_lead.rs, bindings/raftgroups_term.rs and the block in INTEGRATION.md
+    python tools/gen_rust_bindings.py            # writes bindings/raftgroups.rs, bindings/raftgroups_lead.rs, bindings/raftgroups_term.rs, bindings/raftgroups_vote.rs and the block in INTEGRATION.md
     python tools/gen_rust_bindings.py --check    # exit 1 if any of them is out of date (tests/test_abi.py runs this)
 
 Everything is derived from the header: `#[repr(C)]` structs, the `extern "C"` block (one declaration per exported
@@ -21,6 +21,8 @@ LEAD_HEADER = os.path.join(ROOT, "include", "raftgroups_lead.h")  # the extensio
 LEAD_RS = os.path.join(ROOT, "bindings", "raftgroups_lead.rs")
 TERM_HEADER = os.path.join(ROOT, "include", "raftgroups_term.h")  # the second extension: rgt_* functions and types, RGT_* constants
 TERM_RS = os.path.join(ROOT, "bindings", "raftgroups_term.rs")
+VOTE_HEADER = os.path.join(ROOT, "include", "raftgroups_vote.h")  # the third extension: rgv_* functions and types, RGV_* constants
+VOTE_RS = os.path.join(ROOT, "bindings", "raftgroups_vote.rs")
 DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED: tools/gen_rust_bindings.py -->", "<!-- END GENERATED -->"
 
@@ -191,50 +193,24 @@ def generate():
     return emit(*parse(open(HEADER, encoding="utf-8").read()))
 
 
-def generate_lead():
-    """bindings/raftgroups_lead.rs: the extension header's constants, structs and rgx_* functions, over the core module's types."""
-    core = strip_comments(open(HEADER, encoding="utf-8").read())
-    known = {m.group(2): camel(m.group(2)) for m in re.finditer(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", core, flags=re.S)}
-    consts, _, structs, funcs, _ = parse(open(LEAD_HEADER, encoding="utf-8").read(), fn_prefix="rgx_", known=known)
-    o = ["// GENERATED from include/raftgroups_lead.h by tools/gen_rust_bindings.py -- do not edit.",
-         "// The leader's clock, an extension of raftgroups.rs (same library). tests/test_lead_clock_host.py checks that it names every",
-         "// rgx_* export of libraftgroups.so with the header's arity.",
-         "#![allow(non_camel_case_types, dead_code)]",
-         "use super::raftgroups::*;", ""]
-    for name, v, ty in consts:
-        o.append(f"pub const {name}: {ty} = {v};")
-    o.append("pub const RG_HANDOFF_NO_LEAD: u64 = u64::MAX;")
-    o.append("")
-    for sname, fields in structs:
-        o += ["#[repr(C)]", f"pub struct {camel(sname)} {{"] + [f"    pub {ident(fname)}: {ft}," for fname, ft in fields] + ["}", ""]
-    o.append('extern "C" {')
-    for name, ret, params in funcs:
-        ps = ", ".join(f"{ident(n) if n else '_'}: {t}" for n, t in params)
-        o.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
-    o += ["}", ""]
-    return "\n".join(o)
-
-
 def struct_names(path):
     src = strip_comments(open(path, encoding="utf-8").read())
     return {m.group(2): camel(m.group(2)) for m in re.finditer(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S)}
 
 
-def generate_term():
-    """bindings/raftgroups_term.rs: the second extension header's constants, structs and rgt_* functions, over the types of the
-    core module and of the first extension."""
-    known = struct_names(HEADER)
-    known.update(struct_names(LEAD_HEADER))
-    consts, _, structs, funcs, _ = parse(open(TERM_HEADER, encoding="utf-8").read(), fn_prefix="rgt_", known=known, const_prefix="RGT_")
-    o = ["// GENERATED from include/raftgroups_term.h by tools/gen_rust_bindings.py -- do not edit.",
-         "// The leader's term gate and the deposition, an extension of raftgroups.rs and raftgroups_lead.rs (same library).",
-         "// tests/test_term_gate_host.py checks that it names every rgt_* export of libraftgroups.so with the header's arity.",
-         "#![allow(non_camel_case_types, dead_code)]",
-         "use super::raftgroups::*;",
-         "use super::raftgroups_lead::*;", ""]
+def generate_extension(header, fn_prefix, const_prefix, below, what, checked_by, extra_consts=()):
+    """The bindings of one extension header: its constants, structs and functions, over the types of the headers `below` it
+    (their generated modules are `use`d). what / checked_by: the two comment lines under the GENERATED line."""
+    known = {}
+    for h in below:
+        known.update(struct_names(h))
+    consts, _, structs, funcs, _ = parse(open(header, encoding="utf-8").read(), fn_prefix=fn_prefix, known=known, const_prefix=const_prefix)
+    o = ["// GENERATED from include/%s by tools/gen_rust_bindings.py -- do not edit." % os.path.basename(header), what, checked_by,
+         "#![allow(non_camel_case_types, dead_code)]"]
+    o += ["use super::%s::*;" % os.path.splitext(os.path.basename(h))[0] for h in below] + [""]
     for name, v, ty in consts:
         o.append(f"pub const {name}: {ty} = {v};")
-    o.append("")
+    o += list(extra_consts) + [""]
     for sname, fields in structs:
         o += ["#[repr(C)]", f"pub struct {camel(sname)} {{"] + [f"    pub {ident(fname)}: {ft}," for fname, ft in fields] + ["}", ""]
     o.append('extern "C" {')
@@ -243,6 +219,29 @@ def generate_term():
         o.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
     o += ["}", ""]
     return "\n".join(o)
+
+
+def generate_lead():
+    """bindings/raftgroups_lead.rs: the extension header's constants, structs and rgx_* functions, over the core module's types."""
+    return generate_extension(LEAD_HEADER, "rgx_", "RGX?_", [HEADER],
+                              "// The leader's clock, an extension of raftgroups.rs (same library). tests/test_lead_clock_host.py checks that it names every",
+                              "// rgx_* export of libraftgroups.so with the header's arity.", ["pub const RG_HANDOFF_NO_LEAD: u64 = u64::MAX;"])
+
+
+def generate_term():
+    """bindings/raftgroups_term.rs: the second extension header's constants, structs and rgt_* functions, over the types of the
+    core module and of the first extension."""
+    return generate_extension(TERM_HEADER, "rgt_", "RGT_", [HEADER, LEAD_HEADER],
+                              "// The leader's term gate and the deposition, an extension of raftgroups.rs and raftgroups_lead.rs (same library).",
+                              "// tests/test_term_gate_host.py checks that it names every rgt_* export of libraftgroups.so with the header's arity.")
+
+
+def generate_vote():
+    """bindings/raftgroups_vote.rs: the third extension header's constants, structs and rgv_* functions, over the types of the
+    core module and of the two extensions before it."""
+    return generate_extension(VOTE_HEADER, "rgv_", "RGV_", [HEADER, LEAD_HEADER, TERM_HEADER],
+                              "// The dense vote step, an extension of raftgroups.rs, raftgroups_lead.rs and raftgroups_term.rs (same library).",
+                              "// tests/test_vote_step_host.py checks that it names every rgv_* export of libraftgroups.so with the header's arity.")
 
 
 def doc_with_block(doc, rs):
@@ -253,7 +252,7 @@ def doc_with_block(doc, rs):
 
 
 def main():
-    rs, lead_rs, term_rs = generate(), generate_lead(), generate_term()
+    rs, lead_rs, term_rs, vote_rs = generate(), generate_lead(), generate_term(), generate_vote()
     doc = open(DOC, encoding="utf-8").read()
     new_doc = doc_with_block(doc, rs)
     if "--check" in sys.argv:
@@ -264,6 +263,8 @@ def main():
             stale.append(LEAD_RS)
         if not os.path.exists(TERM_RS) or open(TERM_RS, encoding="utf-8").read() != term_rs:
             stale.append(TERM_RS)
+        if not os.path.exists(VOTE_RS) or open(VOTE_RS, encoding="utf-8").read() != vote_rs:
+            stale.append(VOTE_RS)
         if new_doc != doc:
             stale.append(DOC)
         if stale:
@@ -274,8 +275,9 @@ def main():
     open(OUT_RS, "w", encoding="utf-8").write(rs)
     open(LEAD_RS, "w", encoding="utf-8").write(lead_rs)
     open(TERM_RS, "w", encoding="utf-8").write(term_rs)
+    open(VOTE_RS, "w", encoding="utf-8").write(vote_rs)
     open(DOC, "w", encoding="utf-8").write(new_doc)
-    print(f"wrote {OUT_RS}, {LEAD_RS}, {TERM_RS} and the generated block of {DOC}")
+    print(f"wrote {OUT_RS}, {LEAD_RS}, {TERM_RS}, {VOTE_RS} and the generated block of {DOC}")
     return 0
 
 
