@@ -316,7 +316,8 @@ extern "C" int rg_create(const rg_config *cfg, rg_engine **out) try {
     h->dev.engine_bytes = off + 2 * zero_bytes + 256 + rg_align(h->stride * 8);
     h->zero_col = reinterpret_cast<u64 *>(h->arena + off);
     h->d_counts = reinterpret_cast<u64 *>(h->arena + off + zero_bytes);
-    h->d_hint_raised = reinterpret_cast<u32 *>(h->arena + off + zero_bytes + 128); // (the reductions use the first 40 of these 256 bytes)
+    static_assert(RG_COUNTS_WORDS * 8 == 256, "the count words are the 256 bytes between the zero column and the scratch");
+    h->d_hint_raised = reinterpret_cast<u32 *>(h->d_counts + RG_COUNTS_HINT);
     h->d_scratch = h->arena + off + zero_bytes + 256;
     h->rhint = reinterpret_cast<u64 *>(h->arena + off + zero_bytes + 256 + rg_align(h->stride * 8));
     RgState &s = h->st;

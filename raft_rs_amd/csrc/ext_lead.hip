@@ -2,6 +2,7 @@
 // check-quorum step-down included, and the way back into the follower arena for a group that stepped down.
 // There is NO CPU fallback anywhere in this file: without a HIP device every entry point fails.
 #include "rg_engine.h"
+#include "rg_handoff_host.h"
 #include "rg_kernels_lead.h"
 
 extern "C" int rgx_lead_clock_enable(rg_engine *h, const rg_lead_clock_config *cfg) try {
@@ -133,69 +134,33 @@ extern "C" int rgx_lead_clock(rg_engine *h, const rg_lead_clock_out *dev_out, ui
     if (!out.beat) out.beat_cap = 0;
     if (!out.down) out.down_cap = 0;
     RG_HIP(hipMemsetAsync(ld->counts, 0, 32, h->stream));
-    const dim3 grid(rg_grid(h->G, 256)), block(256);
-    u64 *read_qterm = h->rd ? h->rd->cols.qterm : nullptr; // a step-down drops the group's pending reads (looked up per call: either enable order)
-    if (rg_ix32(h->st, h->P)) hipLaunchKernelGGL(k_lead_clock<u32>, grid, block, 0, h->stream, h->st, ld->cols, h->P, out, ld->counts, read_qterm);
-    else hipLaunchKernelGGL(k_lead_clock<u64>, grid, block, 0, h->stream, h->st, ld->cols, h->P, out, ld->counts, read_qterm);
+    RG_LAUNCH_IX(h, k_lead_clock, rg_grid(h->G, 256), h->st, ld->cols, h->P, out, ld->counts, rg_read_qterm(h));
     if (int rc = rg_launch_check("rgx_lead_clock")) return rc;
-    bool cfg_written = true; // (an asynchronous call cannot know)
-    if (host_counts) {
-        RG_HIP(hipMemcpyAsync(host_counts, ld->counts, 32, hipMemcpyDeviceToHost, h->stream));
-        RG_HIP(hipStreamSynchronize(h->stream));
-        cfg_written = host_counts[2] || host_counts[3];
-    }
+    if (int rc = rg_fetch_counts(h, host_counts, ld->counts, 32)) return rc;
+    const bool cfg_written = !host_counts || host_counts[2] || host_counts[3]; // (an asynchronous call cannot know)
     if (cfg_written && h->host_mirror) h->host_cfg_valid = false; // transferee bits may be gone: the mirror re-reads its copy
     return RG_OK;
 } RG_ABI_GUARD
 
 // ---- the way back into the arena ----
-static int rg_step_down_state(rg_engine *h, const char *who) {
-    if (!h->fo || !h->fo->has(RG_FL_ELECT)) return rg_fail(RG_ERR_STATE, "%s: rg_follow_elect_enable first", who);
-    return RG_OK;
-}
-
 extern "C" int rgx_follow_step_down(rg_engine *h, const rg_handoff_rec *host_recs, uint64_t n, rg_handoff_resp *host_resp) try {
     if (!h || (n && (!host_recs || !host_resp))) return rg_fail(RG_ERR_INVALID_ARG, "rgx_follow_step_down: bad argument");
-    if (int src = rg_step_down_state(h, "rgx_follow_step_down")) return src;
-    RgFollowEngine *fo = h->fo;
-    RgSeen seen_f, seen_l;
-    for (u64 i = 0; i < n; i++) {
-        const rg_handoff_rec &q = host_recs[i];
-        if (q.follow_group >= fo->cols.n || q.lead_group >= h->G)
-            return rg_fail(RG_ERR_INVALID_ARG, "rgx_follow_step_down: record %llu: follow group %llu of %llu, lead group %llu of %llu", (unsigned long long)i,
-                           (unsigned long long)q.follow_group, (unsigned long long)fo->cols.n, (unsigned long long)q.lead_group, (unsigned long long)h->G);
-        if (int rc = rg_named_once("rgx_follow_step_down (follow)", seen_f.emplace(q.follow_group, i), i)) return rc;
-        if (int rc = rg_named_once("rgx_follow_step_down (lead)", seen_l.emplace(q.lead_group, i), i)) return rc;
-    }
+    if (int src = rg_elect_enabled(h, "rgx_follow_step_down")) return src;
+    if (int crc = rg_walk_pairs(h, "rgx_follow_step_down", host_recs, n, RG_WALK_SIDE_IN_WHO)) return crc;
     if (n == 0) return RG_OK;
     RG_ENTER(h);
-    RgLayout lay;
-    lay.add(n * sizeof(rg_handoff_rec));
-    const size_t off_resp = lay.add(n * sizeof(rg_handoff_resp));
-    fo->stage.assign(lay.total, 0);
-    memcpy(fo->stage.data(), host_recs, n * sizeof(rg_handoff_rec));
-    const RgLeadCols cells = h->ld ? h->ld->cols : RgLeadCols{}; // (cell == nullptr: the clock layer is off)
-    return rg_follow_round_trip(h, "rgx_follow_step_down", fo->stage.data(), lay.total, [&](char *d) {
-        const rg_handoff_rec *d_recs = reinterpret_cast<const rg_handoff_rec *>(d);
-        rg_handoff_resp *d_resp = reinterpret_cast<rg_handoff_resp *>(d + off_resp);
-        const dim3 grid(rg_grid(n, 256)), block(256);
-        if (rg_ix32(h->st, h->P)) hipLaunchKernelGGL(k_handoff_step_down_list<u32>, grid, block, 0, h->stream, h->st, fo->cols, fo->soft, fo->elect, cells, d_recs, n, d_resp);
-        else hipLaunchKernelGGL(k_handoff_step_down_list<u64>, grid, block, 0, h->stream, h->st, fo->cols, fo->soft, fo->elect, cells, d_recs, n, d_resp);
-    }, {{host_resp, off_resp, n * sizeof(rg_handoff_resp)}});
+    const RgArenaCols c = rg_arena_cols(h);
+    return rg_list_round_trip(h, "rgx_follow_step_down", host_recs, n, host_resp, [&](const rg_handoff_rec *d_recs, rg_handoff_resp *d_resp) {
+        RG_LAUNCH_IX(h, k_handoff_step_down_list, rg_grid(n, 256), c, d_recs, n, d_resp);
+    });
 } RG_ABI_GUARD
 
 extern "C" int rgx_follow_step_down_device(rg_engine *h, const uint8_t *dev_events, const uint64_t *dev_lead, const rg_handoff_out *dev_out) try {
     if (!h || !dev_events || !dev_lead || !dev_out) return rg_fail(RG_ERR_INVALID_ARG, "rgx_follow_step_down_device: bad argument");
-    if (int src = rg_step_down_state(h, "rgx_follow_step_down_device")) return src;
+    if (int src = rg_elect_enabled(h, "rgx_follow_step_down_device")) return src;
     if (h->host_mirror) return rg_fail(RG_ERR_STATE, "rgx_follow_step_down_device: the engine has a host mirror; rgx_follow_step_down");
-    if (!dev_out->status || !dev_out->term || !dev_out->last_index) return rg_fail(RG_ERR_INVALID_ARG, "rgx_follow_step_down_device: an output column is NULL");
+    if (!rg_handoff_out_complete(*dev_out)) return rg_fail(RG_ERR_INVALID_ARG, "rgx_follow_step_down_device: an output column is NULL");
     RG_ENTER(h);
-    RgFollowEngine *fo = h->fo;
-    const RgLeadCols cells = h->ld ? h->ld->cols : RgLeadCols{}; // (cell == nullptr: the clock layer is off)
-    const dim3 grid(rg_grid(fo->cols.n, 256)), block(256);
-    if (rg_ix32(h->st, h->P))
-        hipLaunchKernelGGL(k_handoff_step_down_dense<u32>, grid, block, 0, h->stream, h->st, fo->cols, fo->soft, fo->elect, cells, dev_events, dev_lead, *dev_out);
-    else
-        hipLaunchKernelGGL(k_handoff_step_down_dense<u64>, grid, block, 0, h->stream, h->st, fo->cols, fo->soft, fo->elect, cells, dev_events, dev_lead, *dev_out);
+    RG_LAUNCH_IX(h, k_handoff_step_down_dense, rg_grid(h->fo->cols.n, 256), rg_arena_cols(h), dev_events, dev_lead, *dev_out);
     return rg_launch_check("rgx_follow_step_down_device");
 } RG_ABI_GUARD

@@ -163,6 +163,19 @@ struct RgLeadEngine {
     std::vector<char> stage;                // host staging of one write / read
 };
 
+// The layout of rg_engine::d_counts, in u64 words. Each user clears its own words before it counts and nobody else's, so what a
+// dense call left there stays until its next call.
+enum {
+    RG_COUNTS_REDUCE = 0, RG_COUNTS_REDUCE_N = 5, // the reductions of abi_tick.hip (the most: rg_msg_stats)
+    RG_COUNTS_TERM = 8, RG_COUNTS_TERM_N = 3,     // rgt_lead_gate_device: groups deposed, stale records, records of groups not led
+    RG_COUNTS_HINT = 16, RG_COUNTS_HINT_N = 1,    // rg_engine::d_hint_raised (a u32: the word's low half)
+    RG_COUNTS_VOTE = 24, RG_COUNTS_VOTE_N = 6,    // rgv_follow_vote_device: requests, grants, rejects, ignored, deposed; the answered list's cursor
+    RG_COUNTS_WORDS = 32                          // what rg_create sets aside
+};
+static_assert(RG_COUNTS_REDUCE + RG_COUNTS_REDUCE_N <= RG_COUNTS_TERM && RG_COUNTS_TERM + RG_COUNTS_TERM_N <= RG_COUNTS_HINT &&
+                  RG_COUNTS_HINT + RG_COUNTS_HINT_N <= RG_COUNTS_VOTE && RG_COUNTS_VOTE + RG_COUNTS_VOTE_N <= RG_COUNTS_WORDS,
+              "the users of d_counts overlap");
+
 // ------------------------------------------------------------------------------------------------
 // engine object
 // ------------------------------------------------------------------------------------------------
@@ -179,9 +192,7 @@ struct rg_engine {
     char *msg_arena;  // device staging for rg_tick(host msgs) / rg_flush (lazy)
     u64 *zero_col;    // [P][stride] zeros, substituted for NULL m_hint / m_rs
     u64 *rhint;       // [P][stride] reject hints after find_conflict_by_term (pre-pass output)
-    u64 *d_counts;    // scratch for reductions: up to 5 x u64 (rg_msg_stats) of the 256 bytes set aside in rg_create; words 8..10 are the
-                      // counts of the last rgt_lead_gate_device (ext_term.hip), words 16..21 those of the last rgv_follow_vote_device and
-                      // its list cursor (ext_vote.hip); no reduction clears either
+    u64 *d_counts;    // scratch for reductions and the dense calls' count words: RG_COUNTS_WORDS x u64, laid out by the RG_COUNTS_* enum above
     void *d_scratch;  // G x 8 B scratch for host<->device result shuttles
     size_t col_off[RG_COL_COUNT];
     RgState st;

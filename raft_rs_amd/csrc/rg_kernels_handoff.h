@@ -1,12 +1,15 @@
-// rg_kernels_handoff.h -- kernels of abi_handoff.hip: the hand-off between the follower arena and the leader columns, one lane per
-// record (the sparse forms) or per followed group (the dense forms), 256-thread blocks. A selected lane gathers scattered cold
-// cells a stride apart -- latency, not bandwidth --, so it issues ALL its loads before its first store (the one-round-trip
-// discipline RgTick::become_leader documents; the lead group's cells come one trip behind dev_lead[g], which names them). The
-// leader columns are addressed with the engine's index width (IX: 32- or 64-bit cell offsets, as the tick's). No LDS, no
-// atomics, plain stores. Included by exactly one abi_*.hip unit (one definition per library).
+// rg_kernels_handoff.h -- kernels of abi_handoff.hip, and what every way back from the leader engine into the follower arena shares
+// (the step-down of rg_kernels_lead.h, the deposition of rg_kernels_term.h, the led half of rg_kernels_vote.h): the layers' columns
+// as one kernel argument, one loader, one storer, one lead-side stop, one rg_handoff_back_one. One lane per record (the sparse
+// forms) or per followed group (the dense forms), 256-thread blocks. A selected lane gathers scattered cold cells a stride apart
+// -- latency, not bandwidth --, so it issues ALL its loads before its first store (the one-round-trip discipline
+// RgTick::become_leader documents; the lead group's cells come one trip behind dev_lead[g], which names them). The leader columns
+// are addressed with the engine's index width (IX: 32- or 64-bit cell offsets, as the tick's). No LDS, no atomics, plain stores.
+// The kernels below are abi_handoff.hip's (one definition per library); everything else is a template or inline.
 #pragma once
 #include "rg_engine.h"
 #include "rg_handoff.h"
+#include "rg_term.h"
 
 RG_D RgHandoffLog rg_handoff_load_log(const RgFollowCols &c, u64 g) {
     RgHandoffLog f;
@@ -24,7 +27,7 @@ RG_D RgHandoffLog rg_handoff_load_log(const RgFollowCols &c, u64 g) {
     }
     return f;
 }
-// ... and a log summary back into the arena's columns (the demotion, the step-down and the deposition end in it)
+// ... and a log summary back into the arena's columns (every way back ends in it)
 RG_D void rg_handoff_store_log(const RgFollowCols &fc, u64 g, const RgHandoffLog &f) {
     fc.committed[g] = f.committed;
     fc.last[g] = f.last;
@@ -115,6 +118,101 @@ template <typename IX> RG_D rg_handoff_resp rg_handoff_demote_one(const RgState 
     const RgHandoffLog f = rg_handoff_export(s);
     rg_handoff_store_log(fc, g, f);
     return rg_handoff_answer(RG_HANDOFF_DONE, l.cur_term, l.hi, l.commit, 0);
+}
+
+// ---- the way back with the soft cells and the lead side: step-down, deposition, the vote's led half ----
+// The layers' columns; lc.cell / read_qterm (RgReadCols::qterm) are null while their layer is off.
+struct RgArenaCols {
+    RgState st;
+    RgFollowCols fc;
+    RgSoftCols sc;
+    RgElectCols ec;
+    RgLeadCols lc;
+    u64 *read_qterm;
+};
+
+// The lead-side stop, idempotent: the clock cell STOPPED WITH the tag of the group's current term -- a promotion the clock has not
+// seen yet (tag != RG_COL_CUR_TERM) must not re-arm the group on the next call. `all` (a deposition; the step-down's clock call did
+// both already): the transferee gone, the group's pending reads dropped (the queue's term stamp) -- else neither the cfg word nor
+// the stamp is touched. -> RGT_GATE_EV_TRANSFER_ABORTED or 0
+struct RgLeadStop {
+    u32 cell, cfg;
+    u64 tag;
+};
+template <typename IX> RG_D RgLeadStop rg_handoff_load_stop(const RgState &st, const RgLeadCols &lc, IX L, bool all) {
+    RgLeadStop c;
+    c.cell = lc.cell ? lc.cell[L] : 0u;
+    c.tag = lc.cell ? lc.tag[L] : 0ULL;
+    c.cfg = all ? rg_at(st.cfg, L) : 0u;
+    return c;
+}
+template <typename IX> RG_D u32 rg_handoff_store_stop(const RgState &st, const RgLeadCols &lc, u64 *read_qterm, IX L, const RgLeadStop &c, u64 cur_term, bool all) {
+    if (lc.cell) {
+        const u32 cell = rg_lead_stop(c.cell, c.tag, cur_term);
+        if (cell != c.cell) lc.cell[L] = cell;
+        if (c.tag != cur_term) lc.tag[L] = cur_term;
+    }
+    if (!all) return 0;
+    u32 cfg = c.cfg;
+    const u32 ev = rg_term_abort_transfer(cfg);
+    if (cfg != c.cfg) rg_at(st.cfg, L) = cfg;
+    if (read_qterm) read_qterm[L] = rg_lead_read_stamp(cur_term); // reset's ReadOnly::new (raft.rs:957)
+    return ev;
+}
+
+// What a lane holds of (follow group g, lead group L) between its loads and its stores
+struct RgBack {
+    RgSoftView s, so; // the arena's soft view (role loaded) and its original
+    RgHandoffWin w;
+    RgHandoffLead l;
+    RgLeadStop stop;
+};
+RG_D void rg_handoff_back_open(RgBack &b, const RgArenaCols &c, u64 g) {
+    b.s = rg_soft_open(c.sc, g);
+    b.so = b.s;
+    b.w.term = b.s.term;
+    b.w.lead = b.s.lead;
+    b.w.role = rg_soft_role(b.s);
+    b.w.self_id = c.ec.self_id[g];
+    b.w.conf = 0;
+}
+// The loader of the lead side (L in range) ...
+template <typename IX> RG_D void rg_handoff_back_load(RgBack &b, const RgArenaCols &c, IX L, bool all) {
+    b.l = rg_handoff_load_lead<IX>(c.st, L);
+    b.stop = rg_handoff_load_stop<IX>(c.st, c.lc, L, all);
+}
+// ... and the storer: the log `f` the arena takes, the soft view where `soft`, the lead-side stop (whose events it returns)
+template <typename IX> RG_D u32 rg_handoff_back_store(const RgArenaCols &c, u64 g, IX L, const RgBack &b, const RgHandoffLog &f, bool soft, bool all) {
+    rg_handoff_store_log(c.fc, g, f);
+    if (soft) rg_soft_close(c.sc, g, b.s, b.so);
+    return rg_handoff_store_stop<IX>(c.st, c.lc, c.read_qterm, L, b.stop, b.l.cur_term, all);
+}
+
+// Lead group L (in range) goes back into follow group g (in range); nothing is written unless the answer is DONE. `how` is a
+// constant at every call site:
+//                          refusals                       soft cells: become_follower(.., 0)     lead-side stop   answered term
+//   RG_BACK_STEP_DOWN      rg_lead_step_down_check        at the unchanged term                  cell and tag     the group's
+//   RG_BACK_DEPOSE         rg_term_depose_check at T      at T                                   all              T
+//   RG_BACK_DEPOSE_SCAN    rg_lead_step_down_check        left to the gated step that follows    all              T
+enum RgBackHow { RG_BACK_STEP_DOWN, RG_BACK_DEPOSE, RG_BACK_DEPOSE_SCAN };
+template <typename IX> RG_D rg_handoff_resp rg_handoff_back_one(const RgArenaCols &c, u64 g, IX L, RgBackHow how, u64 T) {
+    const bool depose = how != RG_BACK_STEP_DOWN, soft = how != RG_BACK_DEPOSE_SCAN;
+    // ---- loads ----
+    RgBack b;
+    rg_handoff_back_open(b, c, g);
+    rg_handoff_back_load<IX>(b, c, L, depose);
+    // ---- arithmetic ----
+    const u32 status = depose ? rg_term_depose_check(b.w, b.l.cur_term, T, soft) : rg_lead_step_down_check(b.w, b.l.cur_term);
+    if (status != RG_HANDOFF_DONE) return rg_handoff_answer(status, 0, 0, 0, 0);
+    rg_follow_state fs;
+    fs.group = g;
+    if (rg_handoff_demote(b.l, fs) != RG_HANDOFF_DONE) return rg_handoff_answer(RG_HANDOFF_FAULT, 0, 0, 0, 0);
+    const RgHandoffLog f = rg_handoff_export(fs);
+    if (how == RG_BACK_DEPOSE) rg_term_depose_soft(c.sc.cfg, g, b.s, T);
+    if (how == RG_BACK_STEP_DOWN) rg_lead_step_down_soft(c.sc.cfg, g, b.s);
+    // ---- stores ----
+    rg_handoff_back_store<IX>(c, g, L, b, f, soft, depose);
+    return rg_handoff_answer(RG_HANDOFF_DONE, depose ? T : b.l.cur_term, b.l.hi, b.l.commit, 0);
 }
 
 // The sparse forms: lane = record (distinct follow groups, distinct lead groups, all in range: checked on the host).

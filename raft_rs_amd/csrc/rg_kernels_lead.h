@@ -1,38 +1,22 @@
 // rg_kernels_lead.h -- kernels of ext_lead.hip: the leader's clock (one lane per group of the leader engine, 256-thread blocks) and
-// the way back into the follower arena (one lane per record or per followed group). A lane issues the loads of a phase before its
-// first store; the cfg word and the flag row are loaded only at an election timeout, the matched cells and the commit index only on
-// a beat with hb_commit. A lane that steps down stores one word more: the term stamp of its group's ReadIndex queue (read_qterm =
-// RgReadCols::qterm, null without that layer), so that the queue's own lazy reset empties it. The per-slot columns are addressed
-// with the engine's index width (IX, as in rg_kernels_handoff.h). The lists are compacted as k_follow_clock does it: a ballot per
-// wave, ONE atomic per wave and list. No LDS, plain stores. Included by exactly one abi_*.hip unit.
+// the way back into the follower arena (one lane per record or per followed group; rg_handoff_back_one of rg_kernels_handoff.h). A
+// lane issues the loads of a phase before its first store; the cfg word and the flag row are loaded only at an election timeout, the
+// matched cells and the commit index only on a beat with hb_commit. A lane that steps down stores one word more: the term stamp of
+// its group's ReadIndex queue (read_qterm = RgReadCols::qterm, null without that layer), so that the queue's own lazy reset empties
+// it. The per-slot columns are addressed with the engine's index width (IX, as in rg_kernels_handoff.h). The lists are compacted as
+// k_follow_clock does it (rg_wave.h): a ballot per wave, ONE atomic per wave and list. No LDS, plain stores. Included by exactly one
+// unit.
 #pragma once
 #include "rg_engine.h"
 #include "rg_kernels_handoff.h"
 #include "rg_lead.h"
+#include "rg_wave.h"
 
-// rg_kernels_term.h (ext_term.hip) reuses rg_lead_append and rg_lead_step_down_one's pieces: it defines RG_LEAD_KERNELS_SHARED_ONLY, which
-// leaves out the kernels that are not templates (one definition per library: they are ext_lead.hip's).
-#ifndef RG_LEAD_KERNELS_SHARED_ONLY
 __global__ __launch_bounds__(256) void k_lead_init(RgLeadCols lc, const u64 *__restrict__ cur_term, u64 G, u64 stride, u32 led) {
     const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
     if (g >= stride) return;
     lc.tag[g] = g < G ? cur_term[g] : 0;
     lc.cell[g] = g < G && led ? 0u : RG_LEAD_CELL_STOPPED;
-}
-
-#endif
-
-// A wave's lanes with `mine` claim consecutive places of list[cap] with one atomic on *count (which ends as the TRUE total); a lane
-// whose place lies within cap writes its group.
-RG_D void rg_lead_append(bool mine, u64 g, u64 *list, u64 cap, unsigned long long *count) {
-    const unsigned long long ballot = __ballot(mine);
-    if (!ballot) return;
-    const u32 lane = threadIdx.x & 63u, leader = (u32)__ffsll(ballot) - 1u;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(count, (unsigned long long)__popcll(ballot));
-    base = __shfl(base, (int)leader);
-    const u64 at = base + (u64)__popcll(ballot & ((1ULL << lane) - 1ULL));
-    if (mine && at < cap) list[at] = g;
 }
 
 template <typename IX>
@@ -73,13 +57,12 @@ __global__ __launch_bounds__(256) void k_lead_clock(RgState st, RgLeadCols lc, u
         }
         out.events[g] = (u8)ev;
     }
-    rg_lead_append((ev & RG_LEAD_EV_BEAT) != 0, g, out.beat, out.beat_cap, &counts[0]);
-    rg_lead_append((ev & RG_LEAD_EV_STEPPED_DOWN) != 0, g, out.down, out.down_cap, &counts[2]);
-    rg_lead_append((ev & RG_LEAD_EV_CHECK_QUORUM) != 0, g, nullptr, 0, &counts[1]);
-    rg_lead_append((ev & RG_LEAD_EV_TRANSFER_ABORTED) != 0, g, nullptr, 0, &counts[3]);
+    rg_wave_append((ev & RG_LEAD_EV_BEAT) != 0, g, out.beat, out.beat_cap, &counts[0]);
+    rg_wave_append((ev & RG_LEAD_EV_STEPPED_DOWN) != 0, g, out.down, out.down_cap, &counts[2]);
+    rg_wave_append((ev & RG_LEAD_EV_CHECK_QUORUM) != 0, g, nullptr, 0, &counts[1]);
+    rg_wave_append((ev & RG_LEAD_EV_TRANSFER_ABORTED) != 0, g, nullptr, 0, &counts[3]);
 }
 
-#ifndef RG_LEAD_KERNELS_SHARED_ONLY
 __global__ __launch_bounds__(256) void k_lead_clock_write(RgLeadCols lc, const rg_lead_clock_cell *__restrict__ recs, u64 n) {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -102,59 +85,20 @@ __global__ __launch_bounds__(256) void k_lead_place(RgLeadCols src, u64 *tag, u3
     cell[i] = src.cell[o];
 }
 
-#endif
-
-// The way back into the arena: lead group L (in range) steps down into follow group g (in range). Nothing is written unless the
-// answer is DONE; `lc` = the clock's columns, lc.cell == nullptr while the clock layer is off. The cell is STOPPED WITH the tag of the
-// group's current term: a promotion the clock has not seen yet (tag != RG_COL_CUR_TERM) must not re-arm the group on the next call.
+// The way back into the arena of a group that stepped down, at its unchanged term
 template <typename IX>
-RG_D rg_handoff_resp rg_lead_step_down_one(const RgState &st, const RgFollowCols &fc, const RgSoftCols &sc, const RgElectCols &ec, const RgLeadCols &lc, u64 g, IX L) {
-    // ---- loads ----
-    RgSoftView s = rg_soft_open(sc, g);
-    const RgSoftView so = s;
-    RgHandoffWin w;
-    w.term = s.term;
-    w.lead = s.lead;
-    w.role = rg_soft_role(s);
-    w.self_id = ec.self_id[g];
-    w.conf = 0;
-    const RgHandoffLead l = rg_handoff_load_lead<IX>(st, L);
-    const u32 cell0 = lc.cell ? lc.cell[L] : 0u;
-    const u64 tag0 = lc.cell ? lc.tag[L] : 0ULL;
-    // ---- arithmetic ----
-    const u32 status = rg_lead_step_down_check(w, l.cur_term);
-    if (status != RG_HANDOFF_DONE) return rg_handoff_answer(status, 0, 0, 0, 0);
-    rg_follow_state fs;
-    fs.group = g;
-    if (rg_handoff_demote(l, fs) != RG_HANDOFF_DONE) return rg_handoff_answer(RG_HANDOFF_FAULT, 0, 0, 0, 0);
-    const RgHandoffLog f = rg_handoff_export(fs);
-    rg_lead_step_down_soft(sc.cfg, g, s);
-    // ---- stores ----
-    rg_handoff_store_log(fc, g, f);
-    rg_soft_close(sc, g, s, so);
-    if (lc.cell) {
-        const u32 cell = rg_lead_stop(cell0, tag0, l.cur_term);
-        if (cell != cell0) lc.cell[L] = cell;
-        if (tag0 != l.cur_term) lc.tag[L] = l.cur_term;
-    }
-    return rg_handoff_answer(RG_HANDOFF_DONE, l.cur_term, l.hi, l.commit, 0);
-}
-
-template <typename IX>
-__global__ __launch_bounds__(256) void k_handoff_step_down_list(RgState st, RgFollowCols fc, RgSoftCols sc, RgElectCols ec, RgLeadCols lc,
-                                                                 const rg_handoff_rec *__restrict__ recs, u64 n, rg_handoff_resp *resp) {
+__global__ __launch_bounds__(256) void k_handoff_step_down_list(RgArenaCols c, const rg_handoff_rec *__restrict__ recs, u64 n, rg_handoff_resp *resp) {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    resp[i] = rg_lead_step_down_one<IX>(st, fc, sc, ec, lc, recs[i].follow_group, (IX)recs[i].lead_group);
+    resp[i] = rg_handoff_back_one<IX>(c, recs[i].follow_group, (IX)recs[i].lead_group, RG_BACK_STEP_DOWN, 0);
 }
 // Lane = followed group. A group without a lead group costs its dev_lead cell and its status byte, an unselected one an event byte more.
 template <typename IX>
-__global__ __launch_bounds__(256) void k_handoff_step_down_dense(RgState st, RgFollowCols fc, RgSoftCols sc, RgElectCols ec, RgLeadCols lc,
-                                                                  const u8 *__restrict__ events, const u64 *__restrict__ lead, rg_handoff_out out) {
+__global__ __launch_bounds__(256) void k_handoff_step_down_dense(RgArenaCols c, const u8 *__restrict__ events, const u64 *__restrict__ lead, rg_handoff_out out) {
     const u64 g = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (g >= fc.n) return;
+    if (g >= c.fc.n) return;
     const u64 L = lead[g];
-    if (L >= st.G) { // no lead group -- or not a group of the engine: nothing is read or written through it
+    if (L >= c.st.G) { // no lead group -- or not a group of the engine: nothing is read or written through it
         out.status[g] = L == RG_HANDOFF_NO_LEAD ? RG_HANDOFF_NONE : RG_HANDOFF_FAULT;
         return;
     }
@@ -162,5 +106,5 @@ __global__ __launch_bounds__(256) void k_handoff_step_down_dense(RgState st, RgF
         out.status[g] = RG_HANDOFF_NONE;
         return;
     }
-    rg_handoff_put(out, g, rg_lead_step_down_one<IX>(st, fc, sc, ec, lc, g, (IX)L));
+    rg_handoff_put(out, g, rg_handoff_back_one<IX>(c, g, (IX)L, RG_BACK_STEP_DOWN, 0));
 }

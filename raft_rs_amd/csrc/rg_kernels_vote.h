@@ -3,36 +3,27 @@
 // decided per WAVE with a ballot, not with k_follow_gate_dense's __syncthreads_or, which costs 256 B of LDS and a barrier: every
 // collective below is a wave's, so a wave is the unit that may leave. A request of a group that is not led runs rg_gate_step on the
 // arena's views: the soft hot cells and the log's hot cells, the cold ones (vote, role, priority, the older runs) only where the
-// arithmetic asks. Only a led group touches the leader columns -- its log summary, one trip behind dev_lead[g] which names them, all loads before the first
-// store -- and only a deposed one stores: the arena's log and soft cells and the lead-side stop of rg_kernels_term.h. The answered
-// list goes through rg_lead_append (a ballot per wave, ONE atomic per wave and tile), the five counts are ballots summed in
-// registers over the tiles a wave walks: one atomic per wave and count that is not zero. No scratch, no LDS. The leader columns are addressed with the engine's index width (IX, as in
-// rg_kernels_term.h). Included by exactly one unit.
+// arithmetic asks. Only a led group touches the leader columns -- its log summary, one trip behind dev_lead[g] which names them,
+// all loads before the first store -- and only a deposed one stores: through the loader and the storer of rg_kernels_handoff.h.
+// The answered list is appended per wave (rg_wave.h: ONE atomic per wave and tile), the five counts are ballots summed in registers
+// over the tiles a wave walks: one atomic per wave and count that is not zero. No scratch, no LDS. The leader columns are addressed
+// with the engine's index width (IX, as in rg_kernels_handoff.h). Included by exactly one unit.
 #pragma once
 #include "rg_engine.h"
-#include "rg_kernels_term.h" // rg_term_load_stop / rg_term_store_stop, rg_lead_append, the hand-off's loaders (templates only)
+#include "rg_kernels_handoff.h"
 #include "rg_vote.h"
-
-// What both forms pass down: the layers' columns; lc.cell / read_qterm are null while their layer is off
-struct RgVoteCols {
-    RgState st;
-    RgFollowCols fc;
-    RgSoftCols sc;
-    RgElectCols ec;
-    RgLeadCols lc;
-    u64 *read_qterm;
-};
+#include "rg_wave.h"
 
 // One well-formed request of follow group g (in range); L = its dev_lead value (RG_HANDOFF_NO_LEAD: none). Nothing is written
 // where the status is FAULT or HOST.
-template <typename IX> RG_D rgv_vote_resp rg_vote_one(const RgVoteCols &c, u64 g, u64 L, const RgVoteReq &m) {
-    RgSoftView s = rg_soft_open(c.sc, g);
-    const RgSoftView so = s;
+template <typename IX> RG_D rgv_vote_resp rg_vote_one(const RgArenaCols &c, u64 g, u64 L, const RgVoteReq &m) {
+    RgBack b;
+    b.s = rg_soft_open(c.sc, g);
+    b.so = b.s;
     bool led = false;
     if (L != RG_HANDOFF_NO_LEAD) {
         if (L >= c.st.G) return rg_vote_fault(); // not a group of the engine: nothing is read or written through it
-        const u64 self_id = c.ec.self_id[g];
-        led = s.lead == self_id && self_id != 0 && rg_vote_win_state(s.lead, self_id, rg_soft_role(s));
+        led = rg_vote_win_state(b.s.lead, c.ec.self_id[g], rg_soft_role(b.s));
     }
     if (!led) { // exactly the gated step (rg_follow.h)
         RgFollowView v = rg_follow_open(c.fc, g);
@@ -47,36 +38,29 @@ template <typename IX> RG_D rgv_vote_resp rg_vote_one(const RgVoteCols &c, u64 g
         r.ext = nullptr;
         r.n_ext = 0;
         rg_follow_resp fr;
-        const rg_follow_gate_resp a = rg_gate_step(c.sc.cfg, g, s, v, r, m.term, m.from, m.priority, m.hdr_flags, fr);
+        const rg_follow_gate_resp a = rg_gate_step(c.sc.cfg, g, b.s, v, r, m.term, m.from, m.priority, m.hdr_flags, fr);
         rg_follow_close(c.fc, g, v, o);
-        rg_soft_close(c.sc, g, s, so);
+        rg_soft_close(c.sc, g, b.s, b.so);
         return rg_vote_answer(fr.status, a.gate, a.events, a.term, fr.commit, fr.log_term, v.last);
     }
     // ---- led: the loads ----
-    const IX Lx = (IX)L;
-    const RgHandoffLead l = rg_handoff_load_lead<IX>(c.st, Lx);
-    const RgTermLeadCells cells = rg_term_load_stop<IX>(c.st, c.lc, Lx);
+    rg_handoff_back_load<IX>(b, c, (IX)L, true);
     // ---- arithmetic ----
     RgHandoffLog f;
     bool depose;
-    rgv_vote_resp a = rg_vote_led_group(c.sc.cfg, g, s, l, c.lc.cell != nullptr, cells.cell, cells.tag, m, f, depose);
+    rgv_vote_resp a = rg_vote_led_group(c.sc.cfg, g, b.s, b.l, c.lc.cell != nullptr, b.stop.cell, b.stop.tag, m, f, depose);
     if (!depose) return a;
     // ---- a deposition: the arena takes the group back at m.term, the lead side is stopped ----
-    rg_handoff_store_log(c.fc, g, f);
-    rg_soft_close(c.sc, g, s, so);
-    if (rg_term_store_stop<IX>(c.st, c.lc, c.read_qterm, Lx, cells, l.cur_term)) a.events |= RGV_VOTE_EV_TRANSFER_ABORTED;
+    if (rg_handoff_back_store<IX>(c, g, (IX)L, b, f, true, true)) a.events |= RGV_VOTE_EV_TRANSFER_ABORTED;
     return a;
 }
-
-// A wave's count of its lanes with `mine` (the same value in every lane)
-RG_D u32 rg_vote_wave_count(bool mine) { return (u32)__popcll(__ballot(mine)); }
 
 // counts: u64 [6] = requests, grants, rejects, ignored, deposed, and the cursor of the answered list. A block walks the tiles of 256
 // groups blockIdx.x, blockIdx.x + gridDim.x, ...: a wave sums its five counts in registers over its tiles and issues ONE atomic per
 // count that is not zero when it is done -- same-line atomics are what bounds this kernel, so their number follows the grid, not
 // the arena. The cursor's atomic stays one per wave and tile with an answered lane, and is not issued without a list.
 template <typename IX>
-__global__ __launch_bounds__(256) void k_vote_dense(RgVoteCols c, rg_follow_msgs ms, const u64 *__restrict__ m_term, const u64 *__restrict__ m_from,
+__global__ __launch_bounds__(256) void k_vote_dense(RgArenaCols c, rg_follow_msgs ms, const u64 *__restrict__ m_term, const u64 *__restrict__ m_from,
                                                      const int64_t *__restrict__ m_priority, const u8 *__restrict__ m_hdr, const u64 *__restrict__ lead, rgv_vote_out out,
                                                      unsigned long long *counts) {
     const u64 n_tiles = (c.fc.n + 255) / 256;
@@ -117,12 +101,12 @@ __global__ __launch_bounds__(256) void k_vote_dense(RgVoteCols c, rg_follow_msgs
             out.events[g] = (u8)a.events;
         }
         const bool grant = a.gate == RG_GATE_VOTE_GRANT, reject = a.gate == RG_GATE_VOTE_REJECT || a.gate == RG_GATE_PREVOTE_LOW;
-        n_req += rg_vote_wave_count(req);
-        n_grant += rg_vote_wave_count(grant);
-        n_reject += rg_vote_wave_count(reject);
-        n_ignored += rg_vote_wave_count(a.gate == RG_GATE_IGNORED);
-        n_deposed += rg_vote_wave_count((a.events & RGV_VOTE_EV_DEPOSED) != 0);
-        if (out.answered_cap) rg_lead_append(grant || reject, g, out.answered, out.answered_cap, &counts[5]); // (uniform: no list, no cursor atomic)
+        n_req += rg_wave_count(req);
+        n_grant += rg_wave_count(grant);
+        n_reject += rg_wave_count(reject);
+        n_ignored += rg_wave_count(a.gate == RG_GATE_IGNORED);
+        n_deposed += rg_wave_count((a.events & RGV_VOTE_EV_DEPOSED) != 0);
+        if (out.answered_cap) rg_wave_append(grant || reject, g, out.answered, out.answered_cap, &counts[5]); // (uniform: no list, no cursor atomic)
     }
     if ((threadIdx.x & 63u) == 0) {
         if (n_req) atomicAdd(&counts[0], (unsigned long long)n_req);
@@ -135,7 +119,7 @@ __global__ __launch_bounds__(256) void k_vote_dense(RgVoteCols c, rg_follow_msgs
 
 // The sparse form: lane i = record i (checked on the host: in range, well-formed, no group twice)
 template <typename IX>
-__global__ __launch_bounds__(256) void k_vote_list(RgVoteCols c, const rgv_vote_rec *__restrict__ recs, u64 n, rgv_vote_resp *resp) {
+__global__ __launch_bounds__(256) void k_vote_list(RgArenaCols c, const rgv_vote_rec *__restrict__ recs, u64 n, rgv_vote_resp *resp) {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const rgv_vote_rec q = recs[i];

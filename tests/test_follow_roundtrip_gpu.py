@@ -22,6 +22,7 @@ pytestmark = pytest.mark.gpu
 N = 300  # followed groups: one full workgroup of 256 lanes and a partial one, inside a stride of 512
 CFG = G.Config(3, flags=G.CHECK_QUORUM | G.PRE_VOTE, seed=77)
 FIRST = 65536  # the first capacity of the record staging
+NO_LEAD = 0xFFFFFFFFFFFFFFFF  # RG_HANDOFF_NO_LEAD: a vote record of a group this store does not lead
 
 
 def align(x):
@@ -213,47 +214,89 @@ def handoff_recs(E, rows):
     return a
 
 
-# call -> (records from rows, [(rows, the message behind "<call>: ")]); rows of the cell writes: (group, role) / (group, self_id);
-# of the campaign: (group, flags); of the hand-off: (follow group, lead group). The engine leads 300 groups and follows 300.
+def depose_recs(E, rows):
+    a = np.zeros(len(rows), dtype=E.DEPOSE_REC_DTYPE)
+    for k, (g, L, reserved) in enumerate(rows):
+        a[k]["follow_group"], a[k]["lead_group"], a[k]["term"], a[k]["reserved"] = g, L, 9, reserved
+    return a
+
+
+def vote_recs(E, rows):
+    a = np.zeros(len(rows), dtype=E.VOTE_REC_DTYPE)
+    for k, (g, L, term) in enumerate(rows):
+        a[k]["follow_group"], a[k]["lead_group"], a[k]["term"], a[k]["from"], a[k]["kind"] = g, L, term, 3, E.FOLLOW_MSG_VOTE
+    return a
+
+
+# call -> (its entry point, records from rows, [(rows, the message behind "<entry point>: " -- or, where it begins with the entry
+# point's name, the whole message)]); rows of the cell writes: (group, role) / (group, self_id); of the campaign: (group, flags); of
+# the hand-off and the step-down: (follow group, lead group); of the deposition: (follow group, lead group, reserved); of the vote:
+# (follow group, lead group, term). The engine leads 300 groups and follows 300.
 TWO_FAULTS = {
-    "follow_soft_write": (soft_recs, [
+    "follow_soft_write": ("rg_follow_soft_write", soft_recs, [
         ([(5, 0), (5, 0), (300, 0)], "records 0 and 1 name group 5"),
         ([(5, 0), (300, 0), (5, 0)], "record 1: group 300 of 300"),
         ([(5, 0), (6, 3), (5, 0)], "record 1 (group 6) breaks rule 1 of rg_follow_soft_check"),
         ([(5, 0), (5, 3), (300, 0)], "record 1 (group 5) breaks rule 1 of rg_follow_soft_check"),  # (the rule stands before the repeat)
         ([(5, 0), (6, 0), (7, 0), (6, 0), (5, 0)], "records 1 and 3 name group 6")]),
-    "follow_elect_write": (elect_recs, [
+    "follow_elect_write": ("rg_follow_elect_write", elect_recs, [
         ([(5, 9), (5, 9), (300, 9)], "records 0 and 1 name group 5"),
         ([(5, 9), (300, 9), (5, 9)], "record 1: group 300 of 300"),
         ([(5, 9), (6, 0), (5, 9)], "record 1 (group 6) breaks rule 1 of rg_follow_elect_check"),
         ([(5, 9), (5, 0), (300, 9)], "record 1 (group 5) breaks rule 1 of rg_follow_elect_check"),
         ([(5, 9), (6, 9), (7, 9), (6, 9), (5, 9)], "records 1 and 3 name group 6")]),
-    "follow_campaign": (campaign_recs, [
+    "follow_campaign": ("rg_follow_campaign", campaign_recs, [
         ([(5, 0), (5, 0), (300, 0)], "records 0 and 1 name group 5"),
         ([(5, 0), (300, 0), (5, 0)], "record 1: group 300 of 300, flags 0, term 0, from 0"),
         ([(5, 0), (6, 1), (5, 0)], "record 1: group 6 of 300, flags 0x1, term 0, from 0"),  # (MsgTimeoutNow without term and sender)
         ([(5, 0), (5, 4), (300, 0)], "record 1: group 5 of 300, flags 0x4, term 0, from 0"),
         ([(5, 0), (6, 0), (7, 0), (6, 0), (5, 0)], "records 1 and 3 name group 6")]),
-    "follow_promote": (handoff_recs, [
+    "follow_promote": ("rg_follow_promote", handoff_recs, [
         ([(5, 7), (5, 8), (300, 9)], "records 0 and 1 name follow group 5"),
         ([(5, 7), (6, 300), (5, 8)], "record 1: follow group 6 of 300, lead group 300 of 300"),
         ([(5, 7), (300, 8), (6, 7)], "record 1: follow group 300 of 300, lead group 8 of 300"),
         ([(5, 7), (5, 7), (6, 300)], "records 0 and 1 name follow group 5"),  # (both repeat: the follow group is looked at first)
         ([(5, 7), (6, 7), (5, 8)], "records 0 and 1 name lead group 7")]),
+    # the three extension calls: the promotion's rows, and the record's own rule in front of a repeat and a range fault
+    "follow_step_down": ("rgx_follow_step_down", handoff_recs, [
+        ([(5, 7), (5, 8), (300, 9)], "rgx_follow_step_down (follow): records 0 and 1 name group 5"),
+        ([(5, 7), (6, 300), (5, 8)], "record 1: follow group 6 of 300, lead group 300 of 300"),
+        ([(5, 7), (300, 8), (6, 7)], "record 1: follow group 300 of 300, lead group 8 of 300"),
+        ([(5, 7), (5, 7), (6, 300)], "rgx_follow_step_down (follow): records 0 and 1 name group 5"),
+        ([(5, 7), (6, 7), (5, 8)], "rgx_follow_step_down (lead): records 0 and 1 name group 7")]),
+    "follow_depose": ("rgt_follow_depose", depose_recs, [
+        ([(5, 7, 0), (5, 8, 0), (300, 9, 0)], "rgt_follow_depose (follow): records 0 and 1 name group 5"),
+        ([(5, 7, 0), (6, 300, 0), (5, 8, 0)], "record 1: follow group 6 of 300, lead group 300 of 300"),
+        ([(5, 7, 0), (300, 8, 0), (6, 7, 0)], "record 1: follow group 300 of 300, lead group 8 of 300"),
+        ([(5, 7, 0), (5, 7, 0), (6, 300, 0)], "rgt_follow_depose (follow): records 0 and 1 name group 5"),
+        ([(5, 7, 0), (6, 7, 0), (5, 8, 0)], "rgt_follow_depose (lead): records 0 and 1 name group 7"),
+        ([(5, 7, 0), (5, 7, 1), (300, 9, 0)], "record 1: reserved is 1"),  # (the rule stands before both repeats)
+        ([(5, 7, 0), (6, 8, 4), (5, 9, 0)], "record 1: reserved is 4")]),
+    "follow_vote": ("rgv_follow_vote", vote_recs, [
+        ([(5, 7, 2), (5, 8, 2), (300, 9, 2)], "rgv_follow_vote (follow): records 0 and 1 name group 5"),
+        ([(5, 7, 2), (6, 300, 2), (5, 8, 2)], "record 1: follow group 6 of 300, lead group 300 of 300"),
+        ([(5, 7, 2), (300, 8, 2), (6, 7, 2)], "record 1: follow group 300 of 300, lead group 8 of 300"),
+        ([(5, 7, 2), (5, 7, 2), (6, 300, 2)], "rgv_follow_vote (follow): records 0 and 1 name group 5"),
+        ([(5, 7, 2), (6, 7, 2), (5, 8, 2)], "rgv_follow_vote (lead): records 0 and 1 name group 7"),
+        ([(5, 7, 2), (5, 7, 0), (300, 9, 2)], "record 1: kind 0x4, term 0, from 3, flags 0x0"),
+        ([(5, 7, 2), (6, 8, 0), (5, 9, 2)], "record 1: kind 0x4, term 0, from 3, flags 0x0"),
+        # (no lead group, twice: not a repeat; the lead group that is one stands behind it)
+        ([(5, NO_LEAD, 2), (6, NO_LEAD, 2), (7, 8, 2), (9, 8, 2)], "rgv_follow_vote (lead): records 2 and 3 name group 8")]),
 }
-TWO_FAULTS["follow_demote"] = TWO_FAULTS["follow_promote"]
+TWO_FAULTS["follow_demote"] = ("rg_follow_demote",) + TWO_FAULTS["follow_promote"][1:]
 
 
 @pytest.mark.parametrize("call", sorted(TWO_FAULTS))
 def test_first_fault_wins(rg, call):
     t = Trip(rg, 6)
     before = t.states()
-    make, table = TWO_FAULTS[call]
+    entry, make, table = TWO_FAULTS[call]
     for rows, text in table:
         with pytest.raises(rg.EngineError) as ei:
             getattr(t.eng, call)(make(t.E, rows))
         assert ei.value.code == t.E.ERR["INVALID_ARG"], (rows, str(ei.value))
-        assert str(ei.value) == "raftgroups error -1: rg_%s: %s" % (call, text), (rows, str(ei.value))
+        want = text if text.startswith(entry) else "%s: %s" % (entry, text)
+        assert str(ei.value) == "raftgroups error -1: " + want, (rows, str(ei.value))
         assert t.states() == before, rows
     t.check_nodes(t.nodes, "after the refusals")
     t.close()

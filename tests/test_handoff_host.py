@@ -259,19 +259,27 @@ def test_every_new_name_is_declared_exported_and_bound(rg):
 
 def test_api_refusals_are_host_checks():
     """What the four calls refuse is decided on the host, before anything is staged or launched: the state checks, the group
-    bounds and the duplicate rules stand in front of RG_ENTER."""
-    src = open(os.path.join(ROOT, "raft_rs_amd", "csrc", "abi_handoff.hip")).read()
-    for fn, needles in (("rg_follow_promote", ("rg_handoff_promote_state", "rg_handoff_check_recs", "RG_ERR_SLOT_BUSY")),
+    bounds and the duplicate rules (the record walk the sparse calls of four units share) stand in front of RG_ENTER."""
+    csrc = os.path.join(ROOT, "raft_rs_amd", "csrc")
+    src = open(os.path.join(csrc, "abi_handoff.hip")).read()
+    for fn, needles in (("rg_follow_promote", ("rg_handoff_promote_state", "rg_walk_pairs", "RG_ERR_SLOT_BUSY")),
                         ("rg_follow_promote_device", ("rg_handoff_promote_state", "h->host_mirror", "rg_handoff_out_complete")),
-                        ("rg_follow_demote", ("!h->fo", "rg_handoff_check_recs")),
+                        ("rg_follow_demote", ("!h->fo", "rg_walk_pairs")),
                         ("rg_follow_demote_device", ("!h->fo", "h->host_mirror", "rg_handoff_out_complete"))):
         body = src[src.index('extern "C" int %s(' % fn):]
         body = body[:body.index("} RG_ABI_GUARD")]
         enter = body.index("RG_ENTER(h)")
         for needle in needles:
             assert 0 <= body.find(needle) < enter, (fn, needle)
-    check = src[src.index("static int rg_handoff_check_recs"):src.index("// Stage the records")]
+    state = src[src.index("static int rg_handoff_promote_state"):src.index("// ... and what a promotion leaves behind")]
+    assert "rg_elect_enabled" in state and "h->ins_arena" in state
+    shared = open(os.path.join(csrc, "rg_handoff_host.h")).read()
+    check = shared[shared.index("static inline int rg_walk_pairs"):shared.index("// The round trip of a sparse call")]
     assert "seen_f.emplace" in check and "seen_l.emplace" in check and "follow_group >= h->fo->cols.n" in check and "lead_group >= h->G" in check
+    assert check.index("lead_group >= h->G") < check.index("rule(q, i)") < check.index("seen_f.emplace") < check.index("seen_l.emplace")
+    assert "RG_ENTER" not in shared  # (nothing of the shared host half enters the engine: its callers do, behind their checks)
+    elect = shared[shared.index("static inline int rg_elect_enabled"):shared.index("static inline bool rg_handoff_out_complete")]
+    assert "!h->fo" in elect and "RG_FL_ELECT" in elect and "RG_ERR_STATE" in elect
 
 
 @pytest.mark.parametrize("P", [3, 8])

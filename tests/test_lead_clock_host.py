@@ -471,8 +471,10 @@ def test_api_refusals_are_host_checks():
                         ("rgx_lead_clock_write", ("!h->ld", "w.group >= h->G", "rg_lead_cell_check", "seen.emplace")),
                         ("rgx_lead_clock_read", ("!h->ld", "host_groups[i] >= h->G")),
                         ("rgx_lead_clock", ("!h->ld", "!dev_out->events")),
-                        ("rgx_follow_step_down", ("rg_step_down_state", "q.follow_group >= fo->cols.n", "q.lead_group >= h->G", "seen_f.emplace", "seen_l.emplace")),
-                        ("rgx_follow_step_down_device", ("rg_step_down_state", "h->host_mirror", "!dev_out->status"))):
+                        # (the election layer, and the record walk with its bounds and duplicate rules: rg_handoff_host.h, which
+                        # tests/test_handoff_host.py reads)
+                        ("rgx_follow_step_down", ("rg_elect_enabled", "rg_walk_pairs")),
+                        ("rgx_follow_step_down_device", ("rg_elect_enabled", "h->host_mirror", "rg_handoff_out_complete"))):
         body = src[src.index('extern "C" int %s(' % fn):]
         body = body[:body.index("} RG_ABI_GUARD")]
         enter = body.index("RG_ENTER(h)")

@@ -334,9 +334,11 @@ def test_api_refusals_are_host_checks():
     int entry point of it ends in RG_ABI_GUARD; the HIP-free header includes rg_lead.h and the extension's public header."""
     src = open(os.path.join(ROOT, "raft_rs_amd", "csrc", "ext_term.hip")).read()
     for fn, needles in (("rgt_lead_gate_device", ("!h->ld", "h->host_mirror", "!dev_out->events", "!dev_out->new_term", "dev_out->down_cap && !dev_out->down")),
-                        ("rgt_follow_depose", ("rg_depose_state", "q.follow_group >= fo->cols.n", "q.lead_group >= h->G", "q.reserved", "seen_f.emplace", "seen_l.emplace")),
-                        ("rgt_follow_depose_device", ("rg_depose_state", "h->host_mirror", "!dev_out->status")),
-                        ("rgt_follow_depose_scan_device", ("rg_depose_state", "h->host_mirror", "!dev_out->status"))):
+                        # (the election layer, and the record walk with its bounds and duplicate rules: rg_handoff_host.h, which
+                        # tests/test_handoff_host.py reads)
+                        ("rgt_follow_depose", ("rg_elect_enabled", "q.reserved", "rg_walk_pairs")),
+                        ("rgt_follow_depose_device", ("rg_elect_enabled", "h->host_mirror", "rg_handoff_out_complete")),
+                        ("rgt_follow_depose_scan_device", ("rg_elect_enabled", "h->host_mirror", "rg_handoff_out_complete"))):
         body = src[src.index('extern "C" int %s(' % fn):]
         body = body[:body.index("} RG_ABI_GUARD")]
         enter = body.index("RG_ENTER(h)")

@@ -599,3 +599,21 @@ def test_mirror_engine_device_inflights_and_state_rules(rg):
             call()
         assert ei.value.code == mixed.E.ERR["STATE"] and "one Config" in str(ei.value)
     mixed.close()
+
+
+def test_the_count_words_outlive_a_log_term_tick_of_an_engine_with_device_inflights(rg):
+    """The count words stay what the vote call left until the next vote call (rgv_follow_vote_counts hands out their device address
+    for that): the pre-pass of a dense log-term tick on an engine with device Inflights clears and copies its hint word, which lies
+    in the same scratch block of the engine -- it must not be one of them."""
+    from test_follow_gate_gpu import device_u64
+    rig, cfg, done = vote_rig(rg, True, max_inflight=4)
+    E, eng = rig.E, rig.eng
+    plain = [(50, G.Msg(G.PREVOTE, 7, 12, index=1, log_term=1)), (60, G.Msg(G.PREVOTE, 7, 12, index=1, log_term=1))]
+    got, counts, _ = dense_vote(eng, E, rig.stride, rig.n, plain)
+    before = device_u64(eng.follow_vote_counts(), 6)
+    assert before[0] == counts[0] == 2 and tuple(before[:5]) == tuple(counts)
+    msgs = rg.MsgBuffers(rig.G, rig.P, eng.stride)  # an empty tick that carries a log-term column
+    msgs.m_logterm = np.zeros((rig.P, eng.stride), dtype=np.uint64)
+    eng.tick(msgs)
+    assert device_u64(eng.follow_vote_counts(), 6) == before
+    rig.close()

@@ -310,17 +310,21 @@ def test_api_refusals_are_host_checks():
     src = open(os.path.join(csrc, "ext_vote.hip")).read()
     for fn, needles in (("rgv_follow_vote_device", ("rg_vote_state", "dev_lead && h->host_mirror", "!dev_out->status", "!dev_out->log_term", "dev_out->answered_cap && !dev_out->answered",
                                                     "!dev_msgs->ent_term", "!dev_term")),
-                        ("rgv_follow_vote", ("rg_vote_state", "q.follow_group >= fo->cols.n", "q.lead_group >= h->G && q.lead_group != RG_HANDOFF_NO_LEAD", "!rg_vote_is_request(q.kind)",
-                                             "q.term == 0", "q.from == 0", "q.flags & ~RG_GATE_FORCE", "seen_f.emplace", "seen_l.emplace"))):
+                        # (the record walk with its bounds and duplicate rules: rg_handoff_host.h, which tests/test_handoff_host.py reads)
+                        ("rgv_follow_vote", ("rg_vote_state", "!rg_vote_is_request(q.kind)", "q.term == 0", "q.from == 0", "q.flags & ~RG_GATE_FORCE",
+                                             'rg_walk_pairs(h, "rgv_follow_vote", host_recs, n, RG_WALK_NO_LEAD_OK | RG_WALK_SIDE_IN_WHO, rule)'))):
         body = src[src.index('extern "C" int %s(' % fn):]
         body = body[:body.index("} RG_ABI_GUARD")]
         enter = body.index("RG_ENTER(h)")
         for needle in needles:
             assert 0 <= body.find(needle) < enter, (fn, needle)
     sparse = src[src.index('extern "C" int rgv_follow_vote('):]
-    assert 0 <= sparse.find("if (h->host_mirror) h->host_cfg_valid = false;") < sparse.index("rg_follow_round_trip(")  # the mirror re-reads its cfg copy
-    state = src[src.index("static int rg_vote_state("):src.index("static RgVoteCols")]
-    assert "RG_FL_ELECT" in state and "RG_GATE_CHECK_QUORUM" in state and state.count("RG_ERR_STATE") == 2
+    assert 0 <= sparse.find("if (h->host_mirror) h->host_cfg_valid = false;") < sparse.index("rg_list_round_trip(")  # the mirror re-reads its cfg copy
+    state = src[src.index("static int rg_vote_state("):src.index('extern "C" int rgv_follow_vote_device(')]
+    assert "rg_elect_enabled" in state and "RG_GATE_CHECK_QUORUM" in state and state.count("RG_ERR_STATE") == 1  # (the other: rg_elect_enabled's)
+    shared = open(os.path.join(csrc, "rg_handoff_host.h")).read()
+    walk = shared[shared.index("static inline int rg_walk_pairs"):shared.index("// The round trip of a sparse call")]
+    assert "no_lead_ok && q.lead_group == RG_HANDOFF_NO_LEAD" in walk and "q.lead_group >= h->G && !no_lead" in walk and "if (!no_lead)" in walk
     hdr = open(os.path.join(csrc, "rg_vote.h")).read()
     assert re.findall(r"#include\s+(\S+)", hdr) == ['"rg_term.h"', '"../../include/raftgroups_vote.h"']
     heads = [l for l in src.split("\n") if l.startswith('extern "C" int ')]
@@ -329,12 +333,16 @@ def test_api_refusals_are_host_checks():
         tail = src[src.index(h):]
         assert tail[:tail.index("{")].rstrip().endswith("try"), h
     assert "__global__" not in src and "k_vote_" not in open(os.path.join(csrc, "ext_term.hip")).read()
-    # the count words: 16..21 of 32; the reductions use the first five, the term gate 8..10
-    at = int(re.search(r"#define RG_VOTE_COUNTS_AT (\d+)", src).group(1))
-    term_at = int(re.search(r"#define RG_TERM_COUNTS_AT (\d+)", open(os.path.join(csrc, "ext_term.hip")).read()).group(1))
-    assert at >= term_at + 3 and at + 6 <= 256 // 8
+    # the count words: six of the 32 that the RG_COUNTS_* enum of rg_engine.h lays out (a static_assert there keeps its users apart);
+    # the reductions use the first five, the term gate three behind them
+    engine_h = open(os.path.join(csrc, "rg_engine.h")).read()
+    at, term_at, hint_at = (int(re.search(r"\bRG_COUNTS_%s = (\d+)," % k, engine_h).group(1)) for k in ("VOTE", "TERM", "HINT"))
+    assert at >= term_at + 3 and at + 6 <= 256 // 8 and not hint_at <= at < hint_at + 1 and "RG_COUNTS_WORDS = 32" in engine_h
+    assert "h->d_counts + RG_COUNTS_VOTE)" in src and "h->d_counts + RG_COUNTS_TERM)" in open(os.path.join(csrc, "ext_term.hip")).read()
+    assert "_COUNTS_AT" not in src + engine_h
     others = "".join(open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".h")) and f not in ("ext_vote.hip", "ext_term.hip"))
-    assert not re.search(r"d_counts\s*\+", others) and not re.search(r"d_counts\[", others)  # every other user starts at word 0
+    # every other user starts at word 0 or at a word the enum names
+    assert not re.search(r"d_counts\s*\+(?!\s*RG_COUNTS_)", others) and not re.search(r"d_counts\[", others)
     for m in re.finditer(r"hipMemsetAsync\(h->d_counts, 0, (\d+)", others):
         assert int(m.group(1)) <= 8 * term_at
     build = open(os.path.join(ROOT, "raft_rs_amd", "build.py")).read()
