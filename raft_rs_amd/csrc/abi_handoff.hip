@@ -11,24 +11,15 @@ static int rg_handoff_promote_state(rg_engine *h, const char *who) {
         return rg_fail(RG_ERR_STATE, "%s: the engine holds device Inflights (max_inflight > 0), whose windows only a tick's send stage empties", who);
     return RG_OK;
 }
-// ... and what a promotion leaves behind on the host side of the engine
-static void rg_handoff_promoted(rg_engine *h) {
-    if (h->pub) h->pub->local_lost = true; // RG_COL_COMMIT was written outside a tick: the published advances no longer describe it
-    h->host_res_valid = false;
-}
+// ... and what a promotion leaves behind on the host side of the engine: rg_handoff_promoted, rg_handoff_registered (rg_handoff_host.h)
 
 extern "C" int rg_follow_promote(rg_engine *h, const rg_handoff_rec *host_recs, uint64_t n, rg_handoff_resp *host_resp) try {
     if (!h || (n && (!host_recs || !host_resp))) return rg_fail(RG_ERR_INVALID_ARG, "rg_follow_promote: bad argument");
     if (int src = rg_handoff_promote_state(h, "rg_follow_promote")) return src;
     if (int crc = rg_walk_pairs(h, "rg_follow_promote", host_recs, n, 0)) return crc;
-    if (h->host_mirror) // events queued for the lead group belong to the old term (rg_local_become_leader's rule)
-        for (u64 i = 0; i < n; i++) {
-            u64 row = 0;
-            memcpy(&row, &h->q_mf[host_recs[i].lead_group * 8], 8);
-            if (row)
-                return rg_fail(RG_ERR_SLOT_BUSY, "rg_follow_promote: record %llu: lead group %llu has events queued (they belong to the old term); rg_flush first",
-                               (unsigned long long)i, (unsigned long long)host_recs[i].lead_group);
-        }
+    if (const u64 i = rg_handoff_first_queued(h, host_recs, n); i < n)
+        return rg_fail(RG_ERR_SLOT_BUSY, "rg_follow_promote: record %llu: lead group %llu has events queued (they belong to the old term); rg_flush first",
+                       (unsigned long long)i, (unsigned long long)host_recs[i].lead_group);
     if (n == 0) return RG_OK;
     RG_ENTER(h);
     RgFollowEngine *fo = h->fo;
@@ -37,12 +28,7 @@ extern "C" int rg_follow_promote(rg_engine *h, const rg_handoff_rec *host_recs, 
     });
     if (rc) return rc;
     rg_handoff_promoted(h);
-    for (u64 i = 0; i < n; i++) {
-        if (host_resp[i].status != RG_HANDOFF_DONE) continue;
-        const u64 L = host_recs[i].lead_group;
-        if (h->host_mirror) h->terms[L] = host_resp[i].term; // RG_COL_CUR_TERM and the registered term of a group belong together
-        if (h->host_cfg_valid) h->host_cfg[L] &= ~(0xfu << 20); // (the transferee, if there was one, is gone)
-    }
+    rg_handoff_registered(h, host_recs, host_resp, n);
     return RG_OK;
 } RG_ABI_GUARD
 

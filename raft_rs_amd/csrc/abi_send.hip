@@ -92,6 +92,12 @@ extern "C" int rg_log_sizes_enable(rg_engine *h, uint32_t window) try {
 // host records -> device staging buffer on the engine's stream (grown on demand; the copy is stream-ordered, the host
 // array may be reused once the call returns: pageable copies are staged by the runtime)
 int rg_stage_records(rg_engine *h, const void *recs, size_t bytes) {
+    if (int rc = rg_stage_reserve(h, bytes)) return rc;
+    RG_HIP(hipMemcpyAsync(h->d_recs, recs, bytes, hipMemcpyHostToDevice, h->stream));
+    return RG_OK;
+}
+// ... the buffer alone, at least `bytes` long: a caller whose kernel writes behind the records it stages reserves the whole first
+int rg_stage_reserve(rg_engine *h, size_t bytes) {
     if (bytes > h->d_recs_cap) {
         RG_HIP(hipStreamSynchronize(h->stream)); // (kernels reading the old buffer)
         if (h->d_recs) (void)hipFree(h->d_recs);
@@ -106,7 +112,6 @@ int rg_stage_records(rg_engine *h, const void *recs, size_t bytes) {
         }
         h->d_recs_cap = cap;
     }
-    RG_HIP(hipMemcpyAsync(h->d_recs, recs, bytes, hipMemcpyHostToDevice, h->stream));
     return RG_OK;
 }
 

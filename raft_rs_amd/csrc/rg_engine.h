@@ -372,6 +372,7 @@ int rg_tick_host_impl(rg_engine *h, const rg_msgs *m, const RgSendReq *send);
 // abi_send.hip
 int rg_send_enqueue(rg_engine *h, uint64_t max_entries_per_msg, uint32_t flags, const u64 *list, u64 n, const u32 *n_ptr);
 int rg_stage_records(rg_engine *h, const void *recs, size_t bytes);
+int rg_stage_reserve(rg_engine *h, size_t bytes);
 int rg_send_materialize(rg_engine *h);
 int rg_ensure_pin_send(rg_engine *h);
 void rg_list_stage_ran(rg_engine *h, u64 max_entries, u32 flags);

@@ -30,6 +30,32 @@ static inline int rg_elect_enabled(rg_engine *h, const char *who) {
 
 static inline bool rg_handoff_out_complete(const rg_handoff_out &o) { return o.status && o.term && o.last_index; }
 
+// The host side of a promotion (abi_handoff.hip, ext_handoff.hip). On an engine with a host mirror, events queued for a lead group
+// belong to the old term (rg_local_become_leader's rule): -> the first record whose lead group has some, n where none has
+static inline u64 rg_handoff_first_queued(const rg_engine *h, const rg_handoff_rec *recs, u64 n) {
+    if (!h->host_mirror) return n;
+    for (u64 i = 0; i < n; i++) {
+        u64 row = 0;
+        memcpy(&row, &h->q_mf[recs[i].lead_group * 8], 8);
+        if (row) return i;
+    }
+    return n;
+}
+// ... what a launched promotion leaves behind
+static inline void rg_handoff_promoted(rg_engine *h) {
+    if (h->pub) h->pub->local_lost = true; // RG_COL_COMMIT was written outside a tick: the published advances no longer describe it
+    h->host_res_valid = false;
+}
+// ... and a sparse one per DONE record
+static inline void rg_handoff_registered(rg_engine *h, const rg_handoff_rec *recs, const rg_handoff_resp *resp, u64 n) {
+    for (u64 i = 0; i < n; i++) {
+        if (resp[i].status != RG_HANDOFF_DONE) continue;
+        const u64 L = recs[i].lead_group;
+        if (h->host_mirror) h->terms[L] = resp[i].term; // RG_COL_CUR_TERM and the registered term of a group belong together
+        if (h->host_cfg_valid) h->host_cfg[L] &= ~(0xfu << 20); // (the transferee, if there was one, is gone)
+    }
+}
+
 // One launch of kernel<IX> with the engine's index width over `blocks` blocks of 256 threads: the argument list is written once.
 #define RG_LAUNCH_IX(h, kernel, blocks, ...)                                                                       \
     do {                                                                                                           \

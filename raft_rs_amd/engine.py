@@ -306,6 +306,9 @@ VOTE_REC_DTYPE = np.dtype([("follow_group", "<u8"), ("lead_group", "<u8"), ("ter
 VOTE_RESP_DTYPE = np.dtype([("term", "<u8"), ("commit", "<u8"), ("log_term", "<u8"), ("last_index", "<u8"), ("gate", "<u4"), ("events", "<u4"),
                             ("status", "<u4"), ("reserved", "<u4")])  # rgv_vote_resp
 assert VOTE_REC_DTYPE.itemsize == 80 and VOTE_RESP_DTYPE.itemsize == 48
+# ... and the promotion into an engine with device Inflights (include/raftgroups_handoff.h: rgh_follow_promote ...)
+HANDOFF_EXT_VERSION = 1  # RGH_HANDOFF_VERSION
+PROMOTE_OUT_FIELDS = ("out", "items", "item_cap", "count")  # rgh_promote_out
 
 
 def elect_conf_make(incoming, outgoing=0, self_slot=0):
@@ -354,6 +357,10 @@ class TermGateOut(C.Structure):  # rgt_lead_gate_out: device pointers and the li
 
 class VoteOut(C.Structure):  # rgv_vote_out: device pointers and the list capacity
     _fields_ = [(k, C.c_uint64 if k.endswith("_cap") else C.c_void_p) for k in VOTE_OUT_FIELDS]
+
+
+class PromoteOut(C.Structure):  # rgh_promote_out: the answer columns, the caller's item list and its count word, all DEVICE memory
+    _fields_ = [("out", HandoffOut), ("items", C.c_void_p), ("item_cap", C.c_uint64), ("count", C.c_void_p)]
 
 
 # every symbol include/raftgroups.h declares: (restype, argtypes)
@@ -470,6 +477,9 @@ SYMBOLS = {
     "rgv_follow_vote_device": (_i, [_vp, C.POINTER(FollowMsgs), _vp, _vp, _vp, _vp, _vp, C.POINTER(VoteOut), _vp]),
     "rgv_follow_vote": (_i, [_vp, _vp, _u64, _vp]),
     "rgv_follow_vote_counts": (_vp, [_vp]),
+    "rgh_handoff_version": (C.c_uint32, []),
+    "rgh_follow_promote": (_i, [_vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp, _u64, C.POINTER(_u64)]),
+    "rgh_follow_promote_device": (_i, [_vp, _vp, _vp, _vp, _u64, C.c_uint32, C.POINTER(PromoteOut)]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -1225,6 +1235,27 @@ class Engine:
         p = self._dev_ptr
         o = HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS])
         self._check(self.L.rg_follow_promote_device(self.h, p(result), p(lead), p(persisted), C.byref(o)))
+
+    def follow_promote_send(self, recs, max_entries_per_msg=0, flags=0, item_cap=None):
+        """rgh_follow_promote: the sparse promotion of an engine with device Inflights -- the promotion, the window resets and the
+        first appends in one launch. -> (HANDOFF_RESP_DTYPE array, the first min(total, item_cap) work items as a SEND_ITEM_DTYPE
+        array, the total number of items). item_cap None = room for every item. Synchronises."""
+        recs = np.ascontiguousarray(recs, dtype=HANDOFF_REC_DTYPE)
+        resp = np.zeros(len(recs), dtype=HANDOFF_RESP_DTYPE)
+        cap = len(recs) * self.n_slots if item_cap is None else int(item_cap)
+        items = np.zeros(cap, dtype=SEND_ITEM_DTYPE)
+        n = C.c_uint64(0)
+        self._check(self.L.rgh_follow_promote(self.h, recs.ctypes.data, len(recs), resp.ctypes.data, int(max_entries_per_msg), int(flags),
+                                              items.ctypes.data if cap else None, cap, C.byref(n)))
+        return resp, items[:min(n.value, cap)], n.value
+
+    def follow_promote_send_device(self, result, lead, out, items, item_cap, count, persisted=None, max_entries_per_msg=0, flags=0):
+        """rgh_follow_promote_device (asynchronous): result / lead / persisted / out as in follow_promote_device; items = a DEVICE
+        buffer of item_cap SEND_ITEM_DTYPE records (None with item_cap 0), count = a DEVICE u32 the call zeroes and then holds the
+        total number of items."""
+        p = self._dev_ptr
+        o = PromoteOut(HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS]), p(items), int(item_cap), p(count))
+        self._check(self.L.rgh_follow_promote_device(self.h, p(result), p(lead), p(persisted), int(max_entries_per_msg), int(flags), C.byref(o)))
 
     def follow_demote(self, recs):
         """Sparse demotion: the arena's log summary of follow_group is refreshed from lead_group (persisted unused) ->
