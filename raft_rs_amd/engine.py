@@ -309,6 +309,15 @@ assert VOTE_REC_DTYPE.itemsize == 80 and VOTE_RESP_DTYPE.itemsize == 48
 # ... and the promotion into an engine with device Inflights (include/raftgroups_handoff.h: rgh_follow_promote ...)
 HANDOFF_EXT_VERSION = 1  # RGH_HANDOFF_VERSION
 PROMOTE_OUT_FIELDS = ("out", "items", "item_cap", "count")  # rgh_promote_out
+# ... and the batched conf change (include/raftgroups_conf.h: rgc_apply_conf ...)
+CONF_VERSION = 1  # RGC_CONF_VERSION
+CONF_NONE, CONF_DONE, CONF_DEMOTED, CONF_NOT_LED, CONF_HOST, CONF_FAULT = 0, 1, 2, 3, 4, 5
+CONF_EV_COMMITTED, CONF_EV_TRANSFER_ABORTED = 0x1, 0x2
+CONF_REC_DTYPE = np.dtype([("group", "<u8"), ("cfg", "<u4"), ("reserved", "<u4")])  # rgc_conf_rec
+CONF_RESP_DTYPE = np.dtype([("commit", "<u8"), ("last_index", "<u8"), ("cfg", "<u4"), ("out", "<u4"), ("n_items", "<u4"), ("status", "u1"),
+                            ("events", "u1"), ("added", "u1"), ("removed", "u1")])  # rgc_conf_resp
+assert CONF_REC_DTYPE.itemsize == 16 and CONF_RESP_DTYPE.itemsize == 32
+CONF_OUT_FIELDS = ("status", "events", "commit", "items", "item_cap", "count")  # rgc_conf_out
 
 
 def elect_conf_make(incoming, outgoing=0, self_slot=0):
@@ -361,6 +370,10 @@ class VoteOut(C.Structure):  # rgv_vote_out: device pointers and the list capaci
 
 class PromoteOut(C.Structure):  # rgh_promote_out: the answer columns, the caller's item list and its count word, all DEVICE memory
     _fields_ = [("out", HandoffOut), ("items", C.c_void_p), ("item_cap", C.c_uint64), ("count", C.c_void_p)]
+
+
+class ConfOut(C.Structure):  # rgc_conf_out: the answer columns, the caller's item list and its count word, all DEVICE memory
+    _fields_ = [(k, C.c_uint64 if k.endswith("_cap") else C.c_void_p) for k in CONF_OUT_FIELDS]
 
 
 # every symbol include/raftgroups.h declares: (restype, argtypes)
@@ -480,6 +493,9 @@ SYMBOLS = {
     "rgh_handoff_version": (C.c_uint32, []),
     "rgh_follow_promote": (_i, [_vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp, _u64, C.POINTER(_u64)]),
     "rgh_follow_promote_device": (_i, [_vp, _vp, _vp, _vp, _u64, C.c_uint32, C.POINTER(PromoteOut)]),
+    "rgc_conf_version": (C.c_uint32, []),
+    "rgc_apply_conf": (_i, [_vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp, _u64, C.POINTER(_u64)]),
+    "rgc_apply_conf_device": (_i, [_vp, _vp, _vp, _u64, C.c_uint32, C.POINTER(ConfOut)]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -1256,6 +1272,34 @@ class Engine:
         p = self._dev_ptr
         o = PromoteOut(HandoffOut(*[p(out.get(k)) for k in HANDOFF_OUT_COLUMNS]), p(items), int(item_cap), p(count))
         self._check(self.L.rgh_follow_promote_device(self.h, p(result), p(lead), p(persisted), int(max_entries_per_msg), int(flags), C.byref(o)))
+
+    def apply_conf(self, recs, max_entries_per_msg=0, flags=0, item_cap=None):
+        """rgc_apply_conf: apply_conf and post_conf_change for the led groups of `recs` (CONF_REC_DTYPE: group, cfg =
+        cfg_make(incoming, outgoing, present=...) with every other field 0) in one launch. -> (CONF_RESP_DTYPE array, positional, the
+        first min(total, item_cap) work items as a SEND_ITEM_DTYPE array, the total number of items). On an engine without device
+        Inflights there are no items (item_cap must stay None or 0). Synchronises."""
+        recs = np.ascontiguousarray(recs, dtype=CONF_REC_DTYPE)
+        resp = np.zeros(len(recs), dtype=CONF_RESP_DTYPE)
+        if not self.max_inflight:
+            if item_cap:
+                raise ValueError("apply_conf: an engine without device Inflights produces no work items")
+            self._check(self.L.rgc_apply_conf(self.h, recs.ctypes.data, len(recs), resp.ctypes.data, int(max_entries_per_msg), int(flags), None, 0, None))
+            return resp, np.zeros(0, dtype=SEND_ITEM_DTYPE), 0
+        cap = len(recs) * self.n_slots if item_cap is None else int(item_cap)
+        items = np.zeros(cap, dtype=SEND_ITEM_DTYPE)
+        n = C.c_uint64(0)
+        self._check(self.L.rgc_apply_conf(self.h, recs.ctypes.data, len(recs), resp.ctypes.data, int(max_entries_per_msg), int(flags),
+                                          items.ctypes.data if cap else None, cap, C.byref(n)))
+        return resp, items[:min(n.value, cap)], n.value
+
+    def apply_conf_device(self, sel, cfg, status, events=None, commit=None, items=None, item_cap=0, count=None, max_entries_per_msg=0, flags=0):
+        """rgc_apply_conf_device (asynchronous): sel = a DEVICE u8 column [n_groups] (0 = not selected), cfg = a DEVICE u32 column of
+        the new words, status (mandatory) / events / commit = DEVICE columns [n_groups]; items = a DEVICE buffer of item_cap
+        SEND_ITEM_DTYPE records (None with item_cap 0), count = a DEVICE u32 the call zeroes and then holds the total number of items
+        (both None on an engine without device Inflights)."""
+        p = self._dev_ptr
+        o = ConfOut(p(status), p(events), p(commit), p(items), int(item_cap), p(count))
+        self._check(self.L.rgc_apply_conf_device(self.h, p(sel), p(cfg), int(max_entries_per_msg), int(flags), C.byref(o)))
 
     def follow_demote(self, recs):
         """Sparse demotion: the arena's log summary of follow_group is refreshed from lead_group (persisted unused) ->
