@@ -318,6 +318,15 @@ CONF_RESP_DTYPE = np.dtype([("commit", "<u8"), ("last_index", "<u8"), ("cfg", "<
                             ("events", "u1"), ("added", "u1"), ("removed", "u1")])  # rgc_conf_resp
 assert CONF_REC_DTYPE.itemsize == 16 and CONF_RESP_DTYPE.itemsize == 32
 CONF_OUT_FIELDS = ("status", "events", "commit", "items", "item_cap", "count")  # rgc_conf_out
+# ... and the batched leader transfer (include/raftgroups_transfer.h: rgm_transfer_leader ...)
+TRANSFER_VERSION = 1  # RGM_TRANSFER_VERSION
+XFER_NONE, XFER_STARTED, XFER_SELF, XFER_IN_PROGRESS, XFER_LEARNER, XFER_NO_PROGRESS, XFER_NOT_LED, XFER_FAULT = range(8)
+XFER_EV_TIMEOUT_NOW, XFER_EV_APPEND, XFER_EV_ABORTED_PREVIOUS = 0x1, 0x2, 0x4
+TRANSFER_REC_DTYPE = np.dtype([("group", "<u8"), ("slot", "<u4"), ("reserved", "<u4")])  # rgm_transfer_rec
+TRANSFER_RESP_DTYPE = np.dtype([("last_index", "<u8"), ("matched", "<u8"), ("cfg", "<u4"), ("n_items", "<u4"), ("status", "u1"), ("events", "u1"),
+                                ("previous", "u1"), ("reserved", "u1"), ("reserved2", "<u4")])  # rgm_transfer_resp
+assert TRANSFER_REC_DTYPE.itemsize == 16 and TRANSFER_RESP_DTYPE.itemsize == 32
+TRANSFER_OUT_FIELDS = ("status", "events", "items", "item_cap", "count")  # rgm_transfer_out
 
 
 def elect_conf_make(incoming, outgoing=0, self_slot=0):
@@ -374,6 +383,10 @@ class PromoteOut(C.Structure):  # rgh_promote_out: the answer columns, the calle
 
 class ConfOut(C.Structure):  # rgc_conf_out: the answer columns, the caller's item list and its count word, all DEVICE memory
     _fields_ = [(k, C.c_uint64 if k.endswith("_cap") else C.c_void_p) for k in CONF_OUT_FIELDS]
+
+
+class TransferOut(C.Structure):  # rgm_transfer_out: the answer columns, the caller's item list and its count word, all DEVICE memory
+    _fields_ = [(k, C.c_uint64 if k.endswith("_cap") else C.c_void_p) for k in TRANSFER_OUT_FIELDS]
 
 
 # every symbol include/raftgroups.h declares: (restype, argtypes)
@@ -496,6 +509,9 @@ SYMBOLS = {
     "rgc_conf_version": (C.c_uint32, []),
     "rgc_apply_conf": (_i, [_vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp, _u64, C.POINTER(_u64)]),
     "rgc_apply_conf_device": (_i, [_vp, _vp, _vp, _u64, C.c_uint32, C.POINTER(ConfOut)]),
+    "rgm_transfer_version": (C.c_uint32, []),
+    "rgm_transfer_leader": (_i, [_vp, _vp, _u64, _vp, _u64, C.c_uint32, _vp, _u64, C.POINTER(_u64)]),
+    "rgm_transfer_leader_device": (_i, [_vp, _vp, _u64, C.c_uint32, C.POINTER(TransferOut)]),
     "rg_set_peers": (_i, [_vp, _u64, C.POINTER(_u64), C.c_uint32, _u64]),
     "rg_step": (_i, [_vp, _u64, C.POINTER(AppendResponse)]),
     "rg_step_bytes": (_i, [_vp, _u64, C.c_char_p, _u64, C.c_uint8]),
@@ -1300,6 +1316,34 @@ class Engine:
         p = self._dev_ptr
         o = ConfOut(p(status), p(events), p(commit), p(items), int(item_cap), p(count))
         self._check(self.L.rgc_apply_conf_device(self.h, p(sel), p(cfg), int(max_entries_per_msg), int(flags), C.byref(o)))
+
+    def transfer_leader(self, recs, max_entries=0, flags=0, item_cap=None):
+        """rgm_transfer_leader: handle_transfer_leader for the led groups of `recs` (TRANSFER_REC_DTYPE: group, slot = the transferee)
+        in one launch. -> (TRANSFER_RESP_DTYPE array, positional, the first min(total, item_cap) work items as a SEND_ITEM_DTYPE
+        array, the total number of items). On an engine without device Inflights there are no items (item_cap must stay None or 0).
+        Synchronises."""
+        recs = np.ascontiguousarray(recs, dtype=TRANSFER_REC_DTYPE)
+        resp = np.zeros(len(recs), dtype=TRANSFER_RESP_DTYPE)
+        if not self.max_inflight:
+            if item_cap:
+                raise ValueError("transfer_leader: an engine without device Inflights produces no work items")
+            self._check(self.L.rgm_transfer_leader(self.h, recs.ctypes.data, len(recs), resp.ctypes.data, int(max_entries), int(flags), None, 0, None))
+            return resp, np.zeros(0, dtype=SEND_ITEM_DTYPE), 0
+        cap = len(recs) if item_cap is None else int(item_cap)
+        items = np.zeros(cap, dtype=SEND_ITEM_DTYPE)
+        n = C.c_uint64(0)
+        self._check(self.L.rgm_transfer_leader(self.h, recs.ctypes.data, len(recs), resp.ctypes.data, int(max_entries), int(flags),
+                                               items.ctypes.data if cap else None, cap, C.byref(n)))
+        return resp, items[:min(n.value, cap)], n.value
+
+    def transfer_leader_device(self, to, status, events=None, items=None, item_cap=0, count=None, max_entries=0, flags=0):
+        """rgm_transfer_leader_device (asynchronous): to = a DEVICE u8 column [n_groups] (0 = not selected, else the transferee's
+        slot + 1), status (mandatory) / events = DEVICE u8 columns [n_groups]; items = a DEVICE buffer of item_cap SEND_ITEM_DTYPE
+        records (None with item_cap 0), count = a DEVICE u32 the call zeroes and then holds the total number of items (both None on
+        an engine without device Inflights)."""
+        p = self._dev_ptr
+        o = TransferOut(p(status), p(events), p(items), int(item_cap), p(count))
+        self._check(self.L.rgm_transfer_leader_device(self.h, p(to), int(max_entries), int(flags), C.byref(o)))
 
     def follow_demote(self, recs):
         """Sparse demotion: the arena's log summary of follow_group is refreshed from lead_group (persisted unused) ->

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Generate the Rust FFI bindings of include/raftgroups.h and of its extension headers include/raftgroups_lead.h,
-include/raftgroups_term.h, include/raftgroups_vote.h, include/raftgroups_handoff.h and include/raftgroups_conf.h.
+include/raftgroups_term.h, include/raftgroups_vote.h, include/raftgroups_handoff.h, include/raftgroups_conf.h and
+include/raftgroups_transfer.h.
 
-    python tools/gen_rust_bindings.py            # writes bindings/raftgroups.rs, bindings/raftgroups_lead.rs, bindings/raftgroups_term.rs, bindings/raftgroups_vote.rs, bindings/raftgroups_handoff.rs, bindings/raftgroups_conf.rs and the block in INTEGRATION.md
+    python tools/gen_rust_bindings.py            # writes bindings/raftgroups.rs, bindings/raftgroups_lead.rs, bindings/raftgroups_term.rs, bindings/raftgroups_vote.rs, bindings/raftgroups_handoff.rs, bindings/raftgroups_conf.rs, bindings/raftgroups_transfer.rs and the block in INTEGRATION.md
     python tools/gen_rust_bindings.py --check    # exit 1 if any of them is out of date (tests/test_abi.py runs this)
 
 Everything is derived from the header: `#[repr(C)]` structs, the `extern "C"` block (one declaration per exported
@@ -27,6 +28,8 @@ HANDOFF_HEADER = os.path.join(ROOT, "include", "raftgroups_handoff.h")  # the fo
 HANDOFF_RS = os.path.join(ROOT, "bindings", "raftgroups_handoff.rs")
 CONF_HEADER = os.path.join(ROOT, "include", "raftgroups_conf.h")  # the fifth extension: rgc_* functions and types, RGC_* constants
 CONF_RS = os.path.join(ROOT, "bindings", "raftgroups_conf.rs")
+TRANSFER_HEADER = os.path.join(ROOT, "include", "raftgroups_transfer.h")  # the sixth extension: rgm_* functions and types, RGM_* constants
+TRANSFER_RS = os.path.join(ROOT, "bindings", "raftgroups_transfer.rs")
 DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED: tools/gen_rust_bindings.py -->", "<!-- END GENERATED -->"
 
@@ -264,6 +267,14 @@ def generate_conf():
                               "// tests/test_conf_change_host.py checks that it names every rgc_* export of libraftgroups.so with the header's arity.")
 
 
+def generate_transfer():
+    """bindings/raftgroups_transfer.rs: the sixth extension header's constants, structs and rgm_* functions, over the core module's
+    types (the header includes raftgroups.h alone)."""
+    return generate_extension(TRANSFER_HEADER, "rgm_", "RGM_", [HEADER],
+                              "// The batched leader transfer (handle_transfer_leader on the device), an extension of raftgroups.rs (same library).",
+                              "// tests/test_transfer_host.py checks that it names every rgm_* export of libraftgroups.so with the header's arity.")
+
+
 def doc_with_block(doc, rs):
     block = f"{BEGIN}\n```rust\n{rs}```\n{END}"
     if BEGIN in doc and END in doc:
@@ -273,6 +284,7 @@ def doc_with_block(doc, rs):
 
 def main():
     rs, lead_rs, term_rs, vote_rs, handoff_rs, conf_rs = generate(), generate_lead(), generate_term(), generate_vote(), generate_handoff(), generate_conf()
+    transfer_rs = generate_transfer()
     doc = open(DOC, encoding="utf-8").read()
     new_doc = doc_with_block(doc, rs)
     if "--check" in sys.argv:
@@ -289,6 +301,8 @@ def main():
             stale.append(HANDOFF_RS)
         if not os.path.exists(CONF_RS) or open(CONF_RS, encoding="utf-8").read() != conf_rs:
             stale.append(CONF_RS)
+        if not os.path.exists(TRANSFER_RS) or open(TRANSFER_RS, encoding="utf-8").read() != transfer_rs:
+            stale.append(TRANSFER_RS)
         if new_doc != doc:
             stale.append(DOC)
         if stale:
@@ -302,8 +316,9 @@ def main():
     open(VOTE_RS, "w", encoding="utf-8").write(vote_rs)
     open(HANDOFF_RS, "w", encoding="utf-8").write(handoff_rs)
     open(CONF_RS, "w", encoding="utf-8").write(conf_rs)
+    open(TRANSFER_RS, "w", encoding="utf-8").write(transfer_rs)
     open(DOC, "w", encoding="utf-8").write(new_doc)
-    print(f"wrote {OUT_RS}, {LEAD_RS}, {TERM_RS}, {VOTE_RS}, {HANDOFF_RS}, {CONF_RS} and the generated block of {DOC}")
+    print(f"wrote {OUT_RS}, {LEAD_RS}, {TERM_RS}, {VOTE_RS}, {HANDOFF_RS}, {CONF_RS}, {TRANSFER_RS} and the generated block of {DOC}")
     return 0
 
 
