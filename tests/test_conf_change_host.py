@@ -42,12 +42,16 @@ def state_of(P, cases):
     return st
 
 
-def oracle_route(O, st, recs, answers, cap, max_entries=0, max_bytes=None, sizes=None):
+def oracle_route(O, st, recs, answers, cap, max_entries=0, max_bytes=None, sizes=None, cl=None, windows=None, added_pflags=M.PROBE | M.PF_RECENT_ACTIVE):
     """ro_store_soa's columns with the membership edit on them (the cfg word's three fields; an added slot's cells = Progress::new
     with recent_active), ro_load_soa, ro_maybe_commit, ro_maybe_send_append(to, allow_empty = committed, max) per peer in slot order
-    with the oracle's own Inflights (empty at the load), the transfer abort of raft.rs:2666-2671 -> (state after, messages, cluster)"""
+    with the oracle's own Inflights (empty at the load), the transfer abort of raft.rs:2666-2671 -> (state after, messages, cluster).
+    cl, windows: a cluster that lives on (tests/test_lead_sequences_host.py) is loaded in place of a new one, and gets back the windows
+    {(group, slot): entries} it held -- but an added slot's, which Progress::new leaves empty; cap 0 (no device Inflights): no
+    sends. added_pflags: the flag byte of an added slot (a mutation of that test changes it)."""
     P = st["n_slots"]
     edited = R.copy_state(st)
+    added = set()
     for (g, W), a in zip(recs, answers):
         if a["status"] not in (M.DONE, M.DEMOTED):
             continue
@@ -57,11 +61,16 @@ def oracle_route(O, st, recs, answers, cap, max_entries=0, max_bytes=None, sizes
                 edited["match"][s, g], edited["next"][s, g] = 0, hi + 1
                 for k in ("pr_commit", "pend_snap", "pend_rs", "gid"):
                     edited[k][s, g] = 0
-                edited["pflags"][g, s] = M.PROBE | M.PF_RECENT_ACTIVE
+                edited["pflags"][g, s] = added_pflags
+                added.add((g, s))
         edited["cfg"][g] = (W & M.FIELDS) | (old & M.KEPT)
-    cl = O.Cluster(st["n_groups"])
+    cl = O.Cluster(st["n_groups"]) if cl is None else cl
     cl.load_soa(edited, term=3, max_inflight=cap)
-    cl.set_own_inflights(True)
+    cl.set_own_inflights(cap > 0)
+    for (g, s), entries in (windows or {}).items():
+        if (g, s) not in added and int(edited["cfg"][g]) >> 24 >> s & 1:
+            for e in entries:
+                cl.L.ro_ins_add(ctypes.byref(cl.L.ro_group_progress(cl.h, g, s + 1).contents.ins), e)
     if max_bytes is not None:
         cl.set_limit_bytes(True)
         for g in range(st["n_groups"]):
@@ -74,7 +83,7 @@ def oracle_route(O, st, recs, answers, cap, max_entries=0, max_bytes=None, sizes
         self_slot, tr = int(edited["cfg"][g]) >> 16 & 7, int(edited["cfg"][g]) >> 20 & 0xF
         committed = bool(cl.maybe_commit(g))
         assert committed == bool(a["events"] & M.EV_COMMITTED), (g, a)
-        for s in range(P):
+        for s in range(P if cap else 0):
             if Wp >> s & 1 and s != self_slot:
                 ok, m = cl.maybe_send_append(g, s + 1, committed, max_bytes if max_bytes is not None else max_entries)
                 if ok:
