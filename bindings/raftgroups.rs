@@ -41,6 +41,7 @@ pub const RG_CACHE_RESIDENT: u32 = 4;
 pub const RG_CFGF_NO_SIZE_CLASSES: u32 = 0x1;
 pub const RG_CFGF_CLASS_BLOCK_ORDER: u32 = 0x2;
 pub const RG_CFGF_IX64: u32 = 0x4;
+pub const RG_CFGF_NO_READ_MIRROR: u32 = 0x8;
 pub const RG_VARIANT_DEFAULT: u32 = 0;
 pub const RG_VARIANT_LANE: u32 = 1;
 pub const RG_VARIANT_LDS: u32 = 2;

@@ -246,6 +246,8 @@ typedef struct {
                                           classes out proportionally (measurement) */
 #define RG_CFGF_IX64 0x4u              /* 64-bit cell offsets on an engine small enough for 32-bit ones: the instantiations
                                           only engines beyond 4 GiB per column reach otherwise (tests run both widths) */
+#define RG_CFGF_NO_READ_MIRROR 0x8u    /* the dense lane tick keeps no packed read mirror of matched / committed_index (4 B per
+                                          slot and group, raftgroups_mirror.h): it loads the two columns in every tick */
 
 #define RG_VARIANT_DEFAULT 0u
 #define RG_VARIANT_LANE 1u /* one lane per group, columns straight into registers */

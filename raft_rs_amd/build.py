@@ -4,8 +4,8 @@
 
 hipcc cross-compiles without a GPU. The tick kernels are compiled once per slot count (csrc/tick_inst.hip,
 -DRG_P=1..8: each object holds the kernels of its slot count and the table of their launchers) in parallel with the ABI units (csrc/abi_*.hip: state / tick /
-send / mirror / wire / publish / placement / read / follow / elect / handoff, along the sections of include/raftgroups.h; csrc/ext_lead.hip, csrc/ext_term.hip, csrc/ext_vote.hip, csrc/ext_handoff.hip, csrc/ext_conf.hip and csrc/ext_transfer.hip: the extension headers include/raftgroups_lead.h, include/raftgroups_term.h, include/raftgroups_vote.h, include/raftgroups_handoff.h, include/raftgroups_conf.h and include/raftgroups_transfer.h), then linked. Everything is built with
--fvisibility=hidden: the exported symbols are exactly the entry points the seven public headers declare (rg_* of raftgroups.h, rgx_* of raftgroups_lead.h, rgt_* of raftgroups_term.h, rgv_* of raftgroups_vote.h, rgh_* of raftgroups_handoff.h, rgc_* of raftgroups_conf.h, rgm_* of raftgroups_transfer.h).
+send / mirror / wire / publish / placement / read / follow / elect / handoff, along the sections of include/raftgroups.h; csrc/ext_lead.hip, csrc/ext_term.hip, csrc/ext_vote.hip, csrc/ext_handoff.hip, csrc/ext_conf.hip, csrc/ext_transfer.hip and csrc/ext_mirror.hip: the extension headers include/raftgroups_lead.h, include/raftgroups_term.h, include/raftgroups_vote.h, include/raftgroups_handoff.h, include/raftgroups_conf.h, include/raftgroups_transfer.h and include/raftgroups_mirror.h), then linked. Everything is built with
+-fvisibility=hidden: the exported symbols are exactly the entry points the eight public headers declare (rg_* of raftgroups.h, rgx_* of raftgroups_lead.h, rgt_* of raftgroups_term.h, rgv_* of raftgroups_vote.h, rgh_* of raftgroups_handoff.h, rgc_* of raftgroups_conf.h, rgm_* of raftgroups_transfer.h, and the one object rgr_mirror_stats of raftgroups_mirror.h).
 The .so is git-ignored but travels with gpurun snapshots.
 """
 import os
@@ -18,12 +18,12 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "libraftgroups.so")
-UNITS = ["abi_state.hip", "abi_tick.hip", "abi_send.hip", "abi_mirror.hip", "abi_wire.hip", "abi_publish.hip", "abi_placement.hip", "abi_read.hip", "abi_follow.hip", "abi_elect.hip", "abi_handoff.hip", "ext_lead.hip", "ext_term.hip", "ext_vote.hip", "ext_handoff.hip", "ext_conf.hip", "ext_transfer.hip"]
-DEPS = UNITS + ["tick_inst.hip", "rg_engine.h", "rg_grow.h", "rg_runs.h", "rg_abi_guard.h", "rg_common.h", "rg_group.h", "rg_send.h", "rg_wire.h", "rg_workload.h", "rg_tick_kernels.h",
+UNITS = ["abi_state.hip", "abi_tick.hip", "abi_send.hip", "abi_mirror.hip", "abi_wire.hip", "abi_publish.hip", "abi_placement.hip", "abi_read.hip", "abi_follow.hip", "abi_elect.hip", "abi_handoff.hip", "ext_lead.hip", "ext_term.hip", "ext_vote.hip", "ext_handoff.hip", "ext_conf.hip", "ext_transfer.hip", "ext_mirror.hip"]
+DEPS = UNITS + ["tick_inst.hip", "rg_engine.h", "rg_grow.h", "rg_runs.h", "rg_abi_guard.h", "rg_common.h", "rg_group.h", "rg_send.h", "rg_wire.h", "rg_workload.h", "rg_tick_kernels.h", "rg_mirror.h",
                 "rg_publish.h", "rg_kernels_quorum.h", "rg_kernels_sparse.h", "rg_kernels_send.h", "rg_kernels_state.h",
                 "rg_kernels_workload.h", "rg_kernels_publish.h", "rg_kernels_placement.h", "rg_read.h", "rg_kernels_read.h", "rg_follow.h", "rg_kernels_follow.h", "rg_elect.h", "rg_kernels_elect.h", "rg_handoff.h", "rg_kernels_handoff.h", "rg_handoff_host.h", "rg_wave.h", "rg_lead.h", "rg_kernels_lead.h", "rg_term.h", "rg_kernels_term.h", "rg_vote.h", "rg_kernels_vote.h", "rg_promote.h", "rg_kernels_promote.h", "rg_conf.h", "rg_kernels_conf.h", "rg_transfer.h", "rg_kernels_transfer.h", os.path.join("..", "..", "include", "raftgroups.h"),
                 os.path.join("..", "..", "include", "raftgroups_lead.h"), os.path.join("..", "..", "include", "raftgroups_term.h"), os.path.join("..", "..", "include", "raftgroups_vote.h"),
-                os.path.join("..", "..", "include", "raftgroups_handoff.h"), os.path.join("..", "..", "include", "raftgroups_conf.h"), os.path.join("..", "..", "include", "raftgroups_transfer.h")]
+                os.path.join("..", "..", "include", "raftgroups_handoff.h"), os.path.join("..", "..", "include", "raftgroups_conf.h"), os.path.join("..", "..", "include", "raftgroups_transfer.h"), os.path.join("..", "..", "include", "raftgroups_mirror.h")]
 ARCH = "gfx950"
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "--offload-arch=" + ARCH, "-Wall", "-Wno-unused-function",
           "-Wno-pass-failed"]

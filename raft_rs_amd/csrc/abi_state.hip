@@ -122,7 +122,7 @@ extern "C" int rg_create(const rg_config *cfg, rg_engine **out) try {
                        (unsigned long long)cfg->n_groups, cfg->n_slots);
     if (cfg->variant > RG_VARIANT_COMPACT) return rg_fail(RG_ERR_INVALID_ARG, "rg_create: unknown variant %u", cfg->variant);
     if (cfg->cache_policy > RG_CACHE_RESIDENT) return rg_fail(RG_ERR_INVALID_ARG, "rg_create: unknown cache_policy %u", cfg->cache_policy);
-    if (cfg->flags & ~(RG_CFGF_NO_SIZE_CLASSES | RG_CFGF_CLASS_BLOCK_ORDER | RG_CFGF_IX64))
+    if (cfg->flags & ~(RG_CFGF_NO_SIZE_CLASSES | RG_CFGF_CLASS_BLOCK_ORDER | RG_CFGF_IX64 | RG_CFGF_NO_READ_MIRROR))
         return rg_fail(RG_ERR_INVALID_ARG, "rg_create: unknown flags %#x", cfg->flags);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -249,11 +249,14 @@ extern "C" int rg_create(const rg_config *cfg, rg_engine **out) try {
         h->dev.engines_on_device = (uint32_t)++g_live_on_device[cfg->device];
         h->counted_live = true;
     }
+    bool want_mirror = false;
     {
         const double mall = (double)h->dev.infinity_cache_bytes; // (asked of the device: rg_query_infinity_cache)
         const double per_group = (double)(24u * h->P + 40u), state = (double)h->G * per_group;
-        const double with_msgs = (double)h->G * (double)(40u * h->P + 48u + (cfg->max_inflight ? 40u * h->P : 0u));
         const bool lane = cfg->variant == RG_VARIANT_DEFAULT || cfg->variant == RG_VARIANT_LANE || cfg->variant == RG_VARIANT_COOP;
+        // (the read mirror, where the engine will keep one, is 4 P B per group more that every tick touches)
+        want_mirror = lane && !(cfg->flags & RG_CFGF_IX64) && rg_fits_u32_offsets(h->P, h->stride) && !cfg->max_inflight && !(cfg->flags & RG_CFGF_NO_READ_MIRROR);
+        const double with_msgs = (double)h->G * (double)(40u * h->P + 48u + (cfg->max_inflight ? 40u * h->P : 0u) + (want_mirror ? 4u * h->P : 0u));
         u32 pol = cfg->cache_policy;
         if (pol == RG_CACHE_AUTO) {
             pol = with_msgs > mall ? RG_CACHE_STREAM_MSGS : RG_CACHE_PLAIN;
@@ -352,6 +355,27 @@ extern "C" int rg_create(const rg_config *cfg, rg_engine **out) try {
     s.pub_off_delta = 0;
     s.pub_cap = 0;
     h->pub = nullptr;
+    // the read mirror of the dense lane tick (rg_mirror.h): 4 B per slot and group, for the engines whose dense tick can be
+    // k_tick_mirror -- the lane variant, 32-bit cell offsets, Inflights on the host, a cache policy that runs the lane kernel in a
+    // cached regime (not everything streamed, no resident range: rg_plan_tick never picks the mirror there). Whether the shard is
+    // placed by size class -- k_tick_classes, no mirror -- is only known from the cfg words, after rg_create. Never read before a
+    // tick has written it. Behind it: the count of waves that stored an escape, and its pinned host copy.
+    if (want_mirror && !h->nt_all && !h->nt_resident) {
+        const size_t mb = rg_align((size_t)h->P * h->stride * 4);
+        e = hipMalloc(&h->mirror, mb + 256);
+        if (e == hipSuccess) e = hipMemset(reinterpret_cast<char *>(h->mirror) + mb, 0, 256);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&h->mirror_esc.host), 64, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            if (h->mirror) (void)hipFree(h->mirror);
+            (void)hipFree(h->arena);
+            rg_drop(h);
+            return rg_fail(RG_ERR_OUT_OF_MEMORY, "rg_create: the read mirror (%zu bytes) could not be set up: %s", mb, hipGetErrorString(e));
+        }
+        *h->mirror_esc.host = 0;
+        h->mirror_esc.count = reinterpret_cast<u32 *>(reinterpret_cast<char *>(h->mirror) + mb);
+        h->dev.engine_bytes += mb + 256;
+    }
     if (cfg->max_inflight) { // Inflights rings + the send stage's work-item list
         const size_t meta_b = rg_align((size_t)h->P * h->stride * 4) + 2 * rg_align((size_t)h->P * h->stride * 8); // meta | head | tail
         const size_t ring_b = rg_align((size_t)h->G * h->P * cfg->max_inflight * 8);
@@ -398,6 +422,8 @@ extern "C" void rg_destroy(rg_engine *h) {
     if (h->pub) (void)rg_comm_destroy(h);
     if (h->arena) (void)hipFree(h->arena);
     if (h->ckpt) (void)hipFree(h->ckpt);
+    if (h->mirror) (void)hipFree(h->mirror);
+    if (h->mirror_esc.host) (void)hipHostFree(h->mirror_esc.host);
     if (h->cls_need) (void)hipFree(h->cls_need);
     if (h->cls_order) (void)hipFree(h->cls_order);
     if (h->ins_arena) (void)hipFree(h->ins_arena);
@@ -438,7 +464,7 @@ extern "C" int rg_set_stream(rg_engine *h, void *hip_stream) try {
 
 extern "C" int rg_sync(rg_engine *h) try {
     if (!h) return rg_fail(RG_ERR_INVALID_ARG, "rg_sync: null engine");
-    RG_ENTER(h);
+    RG_ENTER_KEEP(h); // (waits only: the read mirror stays)
     RG_HIP(hipStreamSynchronize(h->stream));
     return RG_OK;
 } RG_ABI_GUARD
@@ -489,7 +515,7 @@ extern "C" int rg_read_column(rg_engine *h, int c, void *dst, uint64_t bytes) tr
     if (bytes != rg_column_bytes(h, c))
         return rg_fail(RG_ERR_INVALID_ARG, "rg_read_column(%d): %llu bytes given, %llu expected", c,
                        (unsigned long long)bytes, (unsigned long long)rg_column_bytes(h, c));
-    RG_ENTER(h);
+    RG_ENTER_KEEP(h); // (a copy out of the arena: the read mirror stays)
     RG_HIP(hipMemcpyAsync(dst, rg_col(h, c), bytes, hipMemcpyDeviceToHost, h->stream));
     RG_HIP(hipStreamSynchronize(h->stream));
     return RG_OK;
@@ -498,6 +524,10 @@ extern "C" int rg_read_column(rg_engine *h, int c, void *dst, uint64_t bytes) tr
 extern "C" void *rg_column_ptr(rg_engine *h, int c) {
     if (!h || c < 0 || c >= RG_COL_COUNT) return nullptr;
     if (c == RG_COL_CFG) h->cls_off = true; // whoever holds this pointer can rewrite cfg words behind the engine's back
+    if (c == RG_COL_MATCH || c == RG_COL_PR_COMMIT || c == RG_COL_COMMIT) { // ... or the cells the read mirror caches
+        h->mirror_off = true;
+        h->mirror_valid = false;
+    }
     return rg_col(h, c);
 }
 

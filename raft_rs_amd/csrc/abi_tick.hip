@@ -161,9 +161,18 @@ static bool rg_lane_variant(const rg_engine *h) {
 
 // What a dense tick will run, decided before anything is launched: the kernel (RG_KERNEL_*), the width of its cell offsets and
 // its memory regime (0 = cached, 1 = message columns streamed, 2 = state columns as well) -- what rg_device_info reports.
+// mirror: the lane kernel runs as k_tick_mirror (rg_mirror.h) -- 1 = it builds the plane from the columns, 2 = it reads the plane;
+// rg_device_info still reports RG_KERNEL_LANE and the regime: the mirror is the engine's own business (rgr_mirror_stats counts).
 struct RgTickPlan {
-    u32 kernel, offset_bits, streaming;
+    u32 kernel, offset_bits, streaming, mirror;
 };
+
+// A graph that holds a captured launch replays it without any entry point: from then on the engine cannot know when the columns
+// the read mirror caches change, so the mirror is off for good (as after rg_column_ptr of one of them).
+static void rg_mirror_note_capture(rg_engine *h) {
+    if (h->mirror && !h->mirror_off && rg_capturing(h, true)) h->mirror_off = true;
+    if (h->mirror_off) h->mirror_valid = false;
+}
 
 static int rg_plan_tick(rg_engine *h, bool send, RgTickPlan *plan) {
     const bool ix32 = rg_ix32(h->st, h->P), gc = h->any_group_commit, lane = rg_lane_variant(h);
@@ -190,7 +199,22 @@ static int rg_plan_tick(rg_engine *h, bool send, RgTickPlan *plan) {
     // (the LDS-staged comparison kernels index with 64 bits at any size; the group-commit instantiation and the LDS / compact
     // variants have no streaming twins: rg_launch_tick_gc)
     *plan = {kernel, (kernel != RG_KERNEL_LDS && ix32) ? 32u : 64u,
-             kernel == RG_KERNEL_SPLIT ? 2u : (kernel == RG_KERNEL_LANE && !gc) ? ntm : 0u};
+             kernel == RG_KERNEL_SPLIT ? 2u : (kernel == RG_KERNEL_LANE && !gc) ? ntm : 0u, 0u};
+    // the read mirror: the lane kernel of a cached regime, no group commit (rg_create made the plane only for engines with 32-bit
+    // cell offsets and no device Inflights), no resident mailbox workgroup ticking on its own, no graph capture
+    if (h->mirror && kernel == RG_KERNEL_LANE && !gc && ntm < 2u && ix32 && !h->mbox_on) {
+        rg_mirror_note_capture(h);
+        // every RG_MIRROR_WINDOW mirror launches: how many waves stored an escape since the last look (the pinned word trails the
+        // device by the launches in flight and by up to 15 waves: a rate, not a count)? More than one in RG_MIRROR_WAVE_SHARE: off
+        if (!h->mirror_off && !h->mirror_escaping && h->mirror_win_launches >= RG_MIRROR_WINDOW) {
+            const u32 now = *(volatile u32 *)h->mirror_esc.host, waves = (u32)((h->G + 63) / 64);
+            h->mirror_escaping = (u64)(now - h->mirror_win_base) * RG_MIRROR_WAVE_SHARE > (u64)h->mirror_win_launches * waves;
+            h->mirror_win_base = now;
+            h->mirror_win_launches = 0;
+        }
+        if (h->mirror_escaping) h->mirror_valid = false;
+        else if (!h->mirror_off) plan->mirror = h->mirror_valid ? 2u : 1u;
+    }
     return RG_OK;
 }
 
@@ -237,13 +261,23 @@ int rg_tick_impl(rg_engine *h, const RgMsgs &ms, const RgSendReq *send) {
     }
     case RG_KERNEL_SPLIT: rode = go.split(h->stream, h->st, ms, h->nt_resident, stop_evt); break;
     default: { // the lane kernel in the engine's memory regime, or the comparison kernel the engine was created with
+        if (plan.mirror) { // ... with the read mirror: built from the columns, or read in their place
+            rode = go.mirror(h->stream, h->st, ms, (int)plan.streaming, h->mirror, h->mirror_esc, plan.mirror == 2u, stop_evt);
+            break;
+        }
         const u32 variant = rg_lane_variant(h) ? (u32)RG_VARIANT_LANE : (u32)h->cfg.variant;
         rode = go.tick(h->stream, h->st, ms, variant | (h->nt_msgs ? RG_VARIANT_NT_MSGS : 0u) | (h->nt_all ? RG_VARIANT_NT_ALL : 0u), gc, stop_evt);
         break;
     }
     }
     hipError_t e = hipGetLastError();
+    h->mirror_valid = false; // (whatever ran wrote the columns; only k_tick_mirror leaves a plane that describes them)
     if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, send ? "tick + send stage launch failed: %s" : "tick launch failed: %s", hipGetErrorString(e));
+    if (plan.mirror) {
+        h->mirror_valid = true;
+        (plan.mirror == 2u ? h->mirror_packed : h->mirror_build)++;
+        h->mirror_win_launches++;
+    }
     if (rode) h->pub_tick_evt = evt_slot;
     rg_after_dense_tick(h, plan);
     if (send) { // what rg_send_appends leaves behind a dense stage
@@ -310,7 +344,7 @@ static int rg_tick_msgs(rg_engine *h, RgMsgs &ms, bool logterm, const RgSendReq 
 }
 
 static int rg_tick_device_impl(rg_engine *h, const rg_msgs *m, const RgSendReq *send) {
-    RG_ENTER_STEP(h, "rg_tick_device");
+    RG_ENTER_STEP_KEEP(h, "rg_tick_device"); // (the message columns are the caller's: nothing of the state is written before the tick)
     RgMsgs ms = rg_msgs_view(h, *m);
     return rg_tick_msgs(h, ms, m->m_logterm != nullptr, send);
 }
@@ -342,6 +376,7 @@ static int rg_fused_run(rg_engine *h, const rg_msgs *m, u32 t0, u32 n, uint32_t 
     fm.commit_t = dev_commit_t ? (u64 *)dev_commit_t + (size_t)t0 * h->G : nullptr;
     fm.n_ticks = n;
     h->launch->fused(h->stream, h->st, fm, h->any_group_commit);
+    h->mirror_valid = false; // (a log-term tick of this call may have run as k_tick_mirror before this launch: the columns move on without the plane)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "fused tick launch failed: %s", hipGetErrorString(e));
     return RG_OK;
@@ -436,7 +471,7 @@ int rg_ensure_msg_arena(rg_engine *h) {
 }
 
 int rg_tick_host_impl(rg_engine *h, const rg_msgs *m, const RgSendReq *send) {
-    RG_ENTER_STEP(h, "rg_tick");
+    RG_ENTER_STEP_KEEP(h, "rg_tick"); // (what follows writes the engine's message staging only, then ticks)
     // pending records live in the engine-owned message columns this tick stages its host columns in: it would wipe them
     if (h->ingested_upper)
         return rg_fail(RG_ERR_STATE, "rg_tick: records are ingested and not ticked yet (rg_ingest): tick them first");
@@ -566,7 +601,7 @@ extern "C" int rg_heartbeat_commits(rg_engine *h, uint64_t *dev_hb, uint64_t *ho
 extern "C" int rg_results(rg_engine *h, uint64_t *host_commit, uint32_t *host_out) try {
     if (!h) return rg_fail(RG_ERR_INVALID_ARG, "rg_results: null engine");
     if (!h->ticked) return rg_fail(RG_ERR_STATE, "rg_results: no tick has run yet");
-    RG_ENTER(h);
+    RG_ENTER_KEEP(h); // (reads only: the read mirror stays)
     if (host_commit) RG_HIP(hipMemcpyAsync(host_commit, h->st.commit, h->G * 8, hipMemcpyDeviceToHost, h->stream));
     if (host_out) RG_HIP(hipMemcpyAsync(host_out, h->st.out, h->G * 4, hipMemcpyDeviceToHost, h->stream));
     RG_HIP(hipStreamSynchronize(h->stream));
@@ -576,7 +611,7 @@ extern "C" int rg_results(rg_engine *h, uint64_t *host_commit, uint32_t *host_ou
 extern "C" int rg_result_counts(rg_engine *h, uint64_t *n_changed, uint64_t *n_fault) try {
     if (!h) return rg_fail(RG_ERR_INVALID_ARG, "rg_result_counts: null engine");
     if (!h->ticked) return rg_fail(RG_ERR_STATE, "rg_result_counts: no tick has run yet");
-    RG_ENTER(h);
+    RG_ENTER_KEEP(h); // (reads only: the read mirror stays)
     u64 c[3];
     const int rc = rg_count_out(h, c);
     if (rc) return rc;
@@ -664,7 +699,7 @@ extern "C" int rg_resolve_host_hints(rg_engine *h, const rg_resolved_hint *items
 
 extern "C" int rg_msg_stats(rg_engine *h, const uint8_t *d_m_flags, uint64_t counts[5]) try {
     if (!h || !d_m_flags || !counts) return rg_fail(RG_ERR_INVALID_ARG, "rg_msg_stats: bad argument");
-    RG_ENTER(h);
+    RG_ENTER_KEEP(h); // (reads only: the read mirror stays)
     RG_HIP(hipMemsetAsync(h->d_counts, 0, 40, h->stream));
     const unsigned grid = rg_grid(h->G, RG_BLOCK) < 1024 ? rg_grid(h->G, RG_BLOCK) : 1024;
     hipLaunchKernelGGL(k_msg_stats, dim3(grid), dim3(RG_BLOCK), 0, h->stream, (const u64 *)d_m_flags,

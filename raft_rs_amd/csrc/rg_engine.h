@@ -62,8 +62,13 @@ int rg_require_hints_resolved(rg_engine *h, const char *who); // abi_tick.hip
 // Every entry point that puts work on the engine's stream starts here: select the device and, if the resident mailbox
 // kernel is on the stream (rg_mailbox_start), tell it to leave -- stream order would make the call wait for it anyway
 // (until its idle timeout), this makes the wait a few microseconds.
+// It also drops the read mirror of the dense lane tick (rg_engine::mirror_valid, rg_mirror.h): whatever this call does, the next
+// dense tick rebuilds the plane from the columns. Dropping is always right; the few entry points that are KNOWN to write none of
+// RG_COL_MATCH / RG_COL_PR_COMMIT / RG_COL_COMMIT -- the dense tick itself, rg_results, rg_result_counts, rg_sync, rg_msg_stats,
+// rg_read_column, the workload generator -- enter through RG_ENTER_KEEP / RG_ENTER_STEP_KEEP, which put the flag back.
 #define RG_ENTER(h)                                                                                \
     do {                                                                                           \
+        (h)->mirror_valid = false;                                                                 \
         (h)->pub_tick_evt = -1; /* (whatever this call enqueues comes behind the last tick's event) */ \
         RG_HIP(hipSetDevice((h)->cfg.device));                                                     \
         int rc__ = rg_mailbox_quiesce(h);                                                          \
@@ -76,6 +81,19 @@ int rg_require_hints_resolved(rg_engine *h, const char *who); // abi_tick.hip
         RG_ENTER(h);                                                                               \
         const int hrc__ = rg_require_hints_resolved(h, who);                                       \
         if (hrc__) return hrc__;                                                                   \
+    } while (0)
+// (a failed entry leaves the mirror dropped)
+#define RG_ENTER_KEEP(h)                                                                           \
+    do {                                                                                           \
+        const bool mv__ = (h)->mirror_valid;                                                       \
+        RG_ENTER(h);                                                                               \
+        (h)->mirror_valid = mv__;                                                                  \
+    } while (0)
+#define RG_ENTER_STEP_KEEP(h, who)                                                                 \
+    do {                                                                                           \
+        const bool mv__ = (h)->mirror_valid;                                                       \
+        RG_ENTER_STEP(h, who);                                                                     \
+        (h)->mirror_valid = mv__;                                                                  \
     } while (0)
 
 // The one switch on the slot count: f(std::integral_constant<int, P>{}), for the launches templated on it that live in the ABI
@@ -290,6 +308,19 @@ struct rg_engine {
     bool host_cfg_valid;
     bool host_mirror;
     struct RgPub *pub; // commit publication across ranks (rg_comm_init), nullptr = single engine
+    // the read mirror of the dense lane tick (rg_mirror.h, k_tick_mirror): engine-internal, no RG_COL_*, in no checkpoint
+    u32 *mirror;        // device: [P][stride] packed words; nullptr = this engine keeps none (rg_create: not the lane variant, 64-bit
+                        // cell offsets, device Inflights, RG_CFGF_NO_READ_MIRROR)
+    bool mirror_valid;  // the plane describes RG_COL_MATCH / RG_COL_PR_COMMIT / RG_COL_COMMIT as they stand: set by the dense tick
+                        // that wrote it, cleared by every other entry (RG_ENTER)
+    bool mirror_off;    // for good: somebody can write those columns without an entry point -- rg_column_ptr handed one of them out,
+                        // or a tick was captured into a graph, which replays it behind the engine's back
+    // escapes, watched without a synchronisation (rg_mirror.h: RgMirrorEsc): the device's running count of waves that stored an
+    // escape, its copy in pinned host memory, and the window rg_plan_tick compares it over
+    RgMirrorEsc mirror_esc;
+    u32 mirror_win_base, mirror_win_launches;
+    bool mirror_escaping; // too many waves escape: k_tick_lane for good (rgr_mirror_info.off = 2)
+    u64 mirror_packed, mirror_build; // launches of k_tick_mirror that read the plane / that (re)built it (rgr_mirror_stats)
 };
 
 // RCCL is bound lazily (the library is ~0.5 GB; single-GPU users never load it). The types come from its header.

@@ -184,6 +184,8 @@ RG_HD void rg_store_group(const RgGroup<P> &r, const RgState &st, IX g) {
     }
 }
 
+#include "rg_mirror.h" // rg_load_group_pk / rg_store_mirror: the read mirror of k_tick_mirror (below)
+
 // RgTick's early stores (rg_group.h: ES) for kernels whose lanes hold consecutive groups and walk the tick together: the same
 // cells rg_store_group would write at the end -- the unconditional / whole-line rules included -- issued as soon as the value
 // is final. The dirty bits are cleared so that nothing is stored twice.
@@ -296,6 +298,32 @@ template <int P, bool GC, typename IX, int NTM = 0> __global__ RG_LANE_BOUNDS(P)
 #endif
     rg_group_tick<P, GC, RG_LANE_NX, false, IX, ES>(r, st, ms, g);
     rg_store_group<P, IX, 3, true, NTM == 2, ES::on>(r, st, g);
+}
+
+// The lane kernel of the cached regimes (NTM 0 / 1, no group commit, 32-bit cell offsets) WITH THE READ MIRROR (rg_mirror.h): the
+// same tick and the same stores as k_tick_lane, then the P packed words of the group. PACKED: the plane is valid (the last thing
+// that touched the engine's state was this kernel) and takes the place of the match / committed_index column loads; otherwise
+// ("build") the group is loaded as k_tick_lane loads it. The host decides per launch (rg_plan_tick, rg_engine::mirror_valid).
+// Its arguments are a struct of their own, so that k_tick_lane's -- and every other kernel's -- stay what they are.
+struct RgMirrorArgs {
+    RgState st;
+    RgMsgs ms;
+    u32 *pk; // [P][stride], peer-major like RG_COL_MATCH
+    RgMirrorEsc esc; // the count of waves that stored an escape (rg_mirror.h)
+};
+template <int P, typename IX, int NTM, bool PACKED> __global__ RG_LANE_BOUNDS(P) void k_tick_mirror(RgMirrorArgs a) {
+    static_assert(NTM == 0 || NTM == 1, "the all-streamed regime keeps k_tick_lane: nothing it touches is touched again in time");
+    typedef typename RgLaneStores<P, false, NTM != 0 || (RG_OPT_NT_MSG != 0)>::type ES;
+    static_assert(!ES::on && !ES::late_pc, "the mirror is encoded from pc[] / mt[] at the end of the tick: no early stores, no late loads");
+    const u64 g64 = (u64)blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (g64 >= a.st.G) return;
+    const IX g = (IX)g64;
+    RgGroup<P> r;
+    if (PACKED) rg_load_group_pk<P, IX, NTM != 0 || (RG_OPT_NT_MSG != 0)>(r, a.st, a.ms, a.pk, g);
+    else rg_load_group<P, RG_LANE_NX, IX, NTM != 0 || (RG_OPT_NT_MSG != 0), false, ES>(r, a.st, a.ms, g);
+    rg_group_tick<P, false, RG_LANE_NX, false, IX, ES>(r, a.st, a.ms, g);
+    rg_store_group<P, IX, 3, true, false, false>(r, a.st, g);
+    rg_mirror_note_escape(rg_store_mirror<P, IX>(r, a.pk, a.st.stride, g), a.esc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1246,6 +1274,9 @@ struct RgTickLaunch {
                              u64 *mflags_rw, const RgListOut &lo, const RgSmallSend &ss);
     void (*mailbox)(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const RgIngest &a0, u32 *ctr_base, u64 *rh,
                     u64 *mflags_rw, const RgListOut &lo, RgMbox *mb, u64 idle_ticks, u64 max_ticks, const RgSmallSend &ss0);
+    // the lane kernel with the read mirror (k_tick_mirror: no group commit, 32-bit cell offsets, ntm 0 or 1: the caller checks all
+    // three); packed = the plane is valid and is read in the place of the match / committed_index columns
+    bool (*mirror)(hipStream_t stream, const RgState &st, const RgMsgs &ms, int ntm, u32 *pk, const RgMirrorEsc &esc, bool packed, hipEvent_t stop_evt);
 };
 template <int P> const RgTickLaunch &rg_tick_launch_p(); // (tick_inst.hip, -DRG_P=P)
 const RgTickLaunch &rg_tick_launch(u32 P);                // (abi_state.hip)
@@ -1328,6 +1359,23 @@ template <int P> bool rg_launch_tick_split_t(hipStream_t stream, const RgState &
     a.ms = ms;
     a.resident_blocks = resident_blocks;
     RG_LAUNCH_TICK((k_tick_split<P, typename RgLaneIx<P>::type>), dim3(rg_grid_for(st.G, RG_BLOCK)), dim3(RG_BLOCK), stream, stop_evt, a);
+    return stop_evt != nullptr;
+}
+template <int P> bool rg_launch_tick_mirror_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, int ntm, u32 *pk, const RgMirrorEsc &esc, bool packed, hipEvent_t stop_evt) {
+    const dim3 grid(rg_grid_for(st.G, RG_BLOCK)), block(RG_BLOCK);
+    RgMirrorArgs a;
+    a.st = st;
+    a.ms = ms;
+    a.pk = pk;
+    a.esc = esc;
+    typedef typename RgLaneIx<P>::type IXP;
+    if (ntm) {
+        if (packed) RG_LAUNCH_TICK((k_tick_mirror<P, IXP, 1, true>), grid, block, stream, stop_evt, a);
+        else RG_LAUNCH_TICK((k_tick_mirror<P, IXP, 1, false>), grid, block, stream, stop_evt, a);
+    } else {
+        if (packed) RG_LAUNCH_TICK((k_tick_mirror<P, IXP, 0, true>), grid, block, stream, stop_evt, a);
+        else RG_LAUNCH_TICK((k_tick_mirror<P, IXP, 0, false>), grid, block, stream, stop_evt, a);
+    }
     return stop_evt != nullptr;
 }
 template <int P>

@@ -9,6 +9,7 @@
 template <> const RgTickLaunch &rg_tick_launch_p<RG_P>() {
     static const RgTickLaunch t = {rg_launch_tick_t<RG_P>,        rg_launch_tick_classes_t<RG_P>, rg_launch_tick_split_t<RG_P>,
                                    rg_launch_tick_list_t<RG_P>,   rg_launch_tick_fused_t<RG_P>,   rg_launch_tick_send_t<RG_P>,
-                                   rg_launch_flush_small_t<RG_P>, rg_launch_flush_small_send_t<RG_P>, rg_launch_mailbox_t<RG_P>};
+                                   rg_launch_flush_small_t<RG_P>, rg_launch_flush_small_send_t<RG_P>, rg_launch_mailbox_t<RG_P>,
+                                   rg_launch_tick_mirror_t<RG_P>};
     return t;
 }

@@ -85,7 +85,7 @@ class CACHE:
 
 class CFGF:
     """rg_config.flags (RG_CFGF_*)."""
-    NO_SIZE_CLASSES, CLASS_BLOCK_ORDER, IX64 = 0x1, 0x2, 0x4
+    NO_SIZE_CLASSES, CLASS_BLOCK_ORDER, IX64, NO_READ_MIRROR = 0x1, 0x2, 0x4, 0x8
 
 
 class KERNEL:
@@ -320,6 +320,7 @@ assert CONF_REC_DTYPE.itemsize == 16 and CONF_RESP_DTYPE.itemsize == 32
 CONF_OUT_FIELDS = ("status", "events", "commit", "items", "item_cap", "count")  # rgc_conf_out
 # ... and the batched leader transfer (include/raftgroups_transfer.h: rgm_transfer_leader ...)
 TRANSFER_VERSION = 1  # RGM_TRANSFER_VERSION
+MIRROR_VERSION = 1  # RGR_MIRROR_VERSION (include/raftgroups_mirror.h)
 XFER_NONE, XFER_STARTED, XFER_SELF, XFER_IN_PROGRESS, XFER_LEARNER, XFER_NO_PROGRESS, XFER_NOT_LED, XFER_FAULT = range(8)
 XFER_EV_TIMEOUT_NOW, XFER_EV_APPEND, XFER_EV_ABORTED_PREVIOUS = 0x1, 0x2, 0x4
 TRANSFER_REC_DTYPE = np.dtype([("group", "<u8"), ("slot", "<u4"), ("reserved", "<u4")])  # rgm_transfer_rec
@@ -383,6 +384,11 @@ class PromoteOut(C.Structure):  # rgh_promote_out: the answer columns, the calle
 
 class ConfOut(C.Structure):  # rgc_conf_out: the answer columns, the caller's item list and its count word, all DEVICE memory
     _fields_ = [(k, C.c_uint64 if k.endswith("_cap") else C.c_void_p) for k in CONF_OUT_FIELDS]
+
+
+class MirrorInfo(C.Structure):  # rgr_mirror_info (include/raftgroups_mirror.h): the dense tick's read mirror, host-side counters
+    _fields_ = [("packed_launches", C.c_uint64), ("build_launches", C.c_uint64), ("plane_bytes", C.c_uint64), ("present", C.c_uint32),
+                ("valid", C.c_uint32), ("off", C.c_uint32), ("version", C.c_uint32)]
 
 
 class TransferOut(C.Structure):  # rgm_transfer_out: the answer columns, the caller's item list and its count word, all DEVICE memory
@@ -575,6 +581,8 @@ def load_library():
     if L.rg_abi_version() != ABI_VERSION:  # (the ABI is source-compatible only: struct layouts follow the header)
         raise ImportError(f"{LIB_PATH} was built with RG_ABI_VERSION {L.rg_abi_version()}, these bindings are written "
                           f"against {ABI_VERSION}: rebuild with `python -m raft_rs_amd.build --force`")
+    # include/raftgroups_mirror.h: rgr_mirror_stats is an exported OBJECT that holds the function's address
+    L.rgr_mirror_stats_fn = C.CFUNCTYPE(_i, _vp, C.POINTER(MirrorInfo))(C.c_void_p.in_dll(L, "rgr_mirror_stats").value)
     _lib = L
     return L
 
@@ -1316,6 +1324,13 @@ class Engine:
         p = self._dev_ptr
         o = ConfOut(p(status), p(events), p(commit), p(items), int(item_cap), p(count))
         self._check(self.L.rgc_apply_conf_device(self.h, p(sel), p(cfg), int(max_entries_per_msg), int(flags), C.byref(o)))
+
+    def mirror_stats(self):
+        """rgr_mirror_stats: the dense tick's read mirror -- launches that read the packed plane, launches that (re)built it, its
+        size, whether it exists / is valid / is off for good. Host-side counters: no device work, the mirror stays as it is."""
+        m = MirrorInfo()
+        self._check(self.L.rgr_mirror_stats_fn(self.h, C.byref(m)))
+        return {k: int(getattr(m, k)) for k, _ in MirrorInfo._fields_ if k != "version"}
 
     def transfer_leader(self, recs, max_entries=0, flags=0, item_cap=None):
         """rgm_transfer_leader: handle_transfer_leader for the led groups of `recs` (TRANSFER_REC_DTYPE: group, slot = the transferee)

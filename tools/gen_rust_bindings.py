@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Generate the Rust FFI bindings of include/raftgroups.h and of its extension headers include/raftgroups_lead.h,
-include/raftgroups_term.h, include/raftgroups_vote.h, include/raftgroups_handoff.h, include/raftgroups_conf.h and
-include/raftgroups_transfer.h.
+include/raftgroups_term.h, include/raftgroups_vote.h, include/raftgroups_handoff.h, include/raftgroups_conf.h,
+include/raftgroups_transfer.h and include/raftgroups_mirror.h.
 
-    python tools/gen_rust_bindings.py            # writes bindings/raftgroups.rs, bindings/raftgroups_lead.rs, bindings/raftgroups_term.rs, bindings/raftgroups_vote.rs, bindings/raftgroups_handoff.rs, bindings/raftgroups_conf.rs, bindings/raftgroups_transfer.rs and the block in INTEGRATION.md
+    python tools/gen_rust_bindings.py            # writes bindings/raftgroups.rs, bindings/raftgroups_lead.rs, bindings/raftgroups_term.rs, bindings/raftgroups_vote.rs, bindings/raftgroups_handoff.rs, bindings/raftgroups_conf.rs, bindings/raftgroups_transfer.rs, bindings/raftgroups_mirror.rs and the block in INTEGRATION.md
     python tools/gen_rust_bindings.py --check    # exit 1 if any of them is out of date (tests/test_abi.py runs this)
 
 Everything is derived from the header: `#[repr(C)]` structs, the `extern "C"` block (one declaration per exported
@@ -30,6 +30,8 @@ CONF_HEADER = os.path.join(ROOT, "include", "raftgroups_conf.h")  # the fifth ex
 CONF_RS = os.path.join(ROOT, "bindings", "raftgroups_conf.rs")
 TRANSFER_HEADER = os.path.join(ROOT, "include", "raftgroups_transfer.h")  # the sixth extension: rgm_* functions and types, RGM_* constants
 TRANSFER_RS = os.path.join(ROOT, "bindings", "raftgroups_transfer.rs")
+MIRROR_HEADER = os.path.join(ROOT, "include", "raftgroups_mirror.h")  # the seventh extension: rgr_* functions and types, RGR_* constants
+MIRROR_RS = os.path.join(ROOT, "bindings", "raftgroups_mirror.rs")
 DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- BEGIN GENERATED: tools/gen_rust_bindings.py -->", "<!-- END GENERATED -->"
 
@@ -220,11 +222,12 @@ def generate_extension(header, fn_prefix, const_prefix, below, what, checked_by,
     o += list(extra_consts) + [""]
     for sname, fields in structs:
         o += ["#[repr(C)]", f"pub struct {camel(sname)} {{"] + [f"    pub {ident(fname)}: {ft}," for fname, ft in fields] + ["}", ""]
-    o.append('extern "C" {')
-    for name, ret, params in funcs:
-        ps = ", ".join(f"{ident(n) if n else '_'}: {t}" for n, t in params)
-        o.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
-    o += ["}", ""]
+    if funcs:  # (a header may declare objects only: extra_consts carries those)
+        o.append('extern "C" {')
+        for name, ret, params in funcs:
+            ps = ", ".join(f"{ident(n) if n else '_'}: {t}" for n, t in params)
+            o.append(f"    pub fn {name}({ps})" + (f" -> {ret}" if ret else "") + ";")
+        o += ["}", ""]
     return "\n".join(o)
 
 
@@ -275,6 +278,15 @@ def generate_transfer():
                               "// tests/test_transfer_host.py checks that it names every rgm_* export of libraftgroups.so with the header's arity.")
 
 
+def generate_mirror():
+    """bindings/raftgroups_mirror.rs: the seventh extension header's constants, structs and rgr_* functions, over the core module's
+    types (the header includes raftgroups.h alone)."""
+    return generate_extension(MIRROR_HEADER, "rgr_", "RGR_", [HEADER],
+                              "// The dense tick's read mirror (its counters), an extension of raftgroups.rs (same library).",
+                              "// tests/test_mirror_host.py checks that it names the rgr_* export of libraftgroups.so -- an OBJECT holding the function's address.",
+                              ['', 'extern "C" {', '    pub static rgr_mirror_stats: unsafe extern "C" fn(h: *const RgEngine, info: *mut RgrMirrorInfo) -> i32;', '}'])
+
+
 def doc_with_block(doc, rs):
     block = f"{BEGIN}\n```rust\n{rs}```\n{END}"
     if BEGIN in doc and END in doc:
@@ -285,6 +297,7 @@ def doc_with_block(doc, rs):
 def main():
     rs, lead_rs, term_rs, vote_rs, handoff_rs, conf_rs = generate(), generate_lead(), generate_term(), generate_vote(), generate_handoff(), generate_conf()
     transfer_rs = generate_transfer()
+    mirror_rs = generate_mirror()
     doc = open(DOC, encoding="utf-8").read()
     new_doc = doc_with_block(doc, rs)
     if "--check" in sys.argv:
@@ -303,6 +316,8 @@ def main():
             stale.append(CONF_RS)
         if not os.path.exists(TRANSFER_RS) or open(TRANSFER_RS, encoding="utf-8").read() != transfer_rs:
             stale.append(TRANSFER_RS)
+        if not os.path.exists(MIRROR_RS) or open(MIRROR_RS, encoding="utf-8").read() != mirror_rs:
+            stale.append(MIRROR_RS)
         if new_doc != doc:
             stale.append(DOC)
         if stale:
@@ -317,8 +332,9 @@ def main():
     open(HANDOFF_RS, "w", encoding="utf-8").write(handoff_rs)
     open(CONF_RS, "w", encoding="utf-8").write(conf_rs)
     open(TRANSFER_RS, "w", encoding="utf-8").write(transfer_rs)
+    open(MIRROR_RS, "w", encoding="utf-8").write(mirror_rs)
     open(DOC, "w", encoding="utf-8").write(new_doc)
-    print(f"wrote {OUT_RS}, {LEAD_RS}, {TERM_RS}, {VOTE_RS}, {HANDOFF_RS}, {CONF_RS}, {TRANSFER_RS} and the generated block of {DOC}")
+    print(f"wrote {OUT_RS}, {LEAD_RS}, {TERM_RS}, {VOTE_RS}, {HANDOFF_RS}, {CONF_RS}, {TRANSFER_RS}, {MIRROR_RS} and the generated block of {DOC}")
     return 0
 
 

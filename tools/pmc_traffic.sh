@@ -11,8 +11,8 @@ rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
 CMD="python $R/bench.py --steps $STEPS --warmup 3 --repeats 1 --no-cpu-baseline --no-extras $*"
-timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/f -o f -- $CMD > /dev/null 2> $O/f.err
-timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/w -o w -- $CMD > /dev/null 2> $O/w.err
+timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/f -o f -- $CMD > /dev/null 2> $O/f.err || { echo "FETCH_SIZE pass failed (rc $?): $(tail -3 $O/f.err)"; exit 1; }
+timeout 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/w -o w -- $CMD > /dev/null 2> $O/w.err || { echo "WRITE_SIZE pass failed (rc $?): $(tail -3 $O/w.err)"; exit 1; }
 python - "$O" "$KEY" "$STEPS" "$*" <<'PY' > $R/gpurun_out/traffic_$TAG.json
 import csv, glob, sys, collections, json, re
 O, key, steps, args = sys.argv[1], sys.argv[2], int(sys.argv[3]), sys.argv[4]
