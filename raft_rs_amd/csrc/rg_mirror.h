@@ -36,10 +36,13 @@ RG_HD u32 rg_mirror_encode(u64 mt, u64 pc, u64 c) {
 RG_HD u64 rg_mirror_match(u32 w, u64 c) { return c + (u64)(int64_t)(int16_t)(w & 0xffffu); }
 RG_HD u64 rg_mirror_prc(u32 w, u64 c) { return c - (u64)(w >> 16); }
 
-// Does any lane of the wave say so? (the host twin: the lane's own answer)
+// Does any lane of the wave say so? (the host twin: the lane's own answer, or -- RG_MIRROR_TWIN_ANY, which only
+// tests/host_check/mirror_twin.hip defines -- the answer the twin worked out for the lane's block of 64 groups beforehand)
 RG_HD bool rg_mirror_any(bool mine) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_ballot_w64(mine) != 0;
+#elif defined(RG_MIRROR_TWIN_ANY)
+    return RG_MIRROR_TWIN_ANY(mine);
 #else
     return mine;
 #endif

@@ -2,6 +2,12 @@
 // rg_load_group_pk, rg_store_mirror -- the exact code k_tick_mirror inlines) compiled for the HOST, beside the plain road
 // (rg_load_group / rg_group_tick / rg_store_group), so a CPU-only test can run both over the same stream and compare every column
 // after every tick. Never part of libraftgroups.so. Build: hipcc -O3 -shared -fPIC --offload-arch=gfx950 mirror_twin.hip -o libmirror_twin.so
+//
+// WAVE mode (mode 3): on the device the escape branch of rg_load_group_pk is decided by the whole 64-lane wave (rg_mirror_any is a
+// ballot), so a lane WITHOUT an escape re-reads its cells too when a neighbour has one. The twin plays that: before it runs the
+// lanes of a block of 64 consecutive groups it works out the block's answer from the plane, and rg_mirror_any returns that.
+static bool twin_wave_mode = false, twin_wave_any = false;
+#define RG_MIRROR_TWIN_ANY(mine) (twin_wave_mode ? twin_wave_any : (mine))
 #include "../../raft_rs_amd/csrc/rg_tick_kernels.h"
 
 // state[]: match next pr_commit pend_snap pend_rs gid pflags commit term_lo term_hi cfg out
@@ -40,7 +46,8 @@ static void twin_derive(const RgState &st, unsigned P) {
     }
 }
 
-// mode 0: the plain road; 1: build (plain loader, then the words); 2: packed (the words in the place of the two columns).
+// mode 0: the plain road; 1: build (plain loader, then the words); 2: packed (the words in the place of the two columns), every
+// lane deciding the escape branch for itself; 3: packed, the block of 64 groups deciding it together (the device's semantics).
 // Exactly k_tick_mirror's sequence in modes 1 and 2 (NTM only picks the load instruction on the device).
 template <int P, typename IX> static void twin_one(const RgState &st, const RgMsgs &ms, u32 *pk, int mode, IX g) {
     RgGroup<P> r;
@@ -54,10 +61,21 @@ template <int P, typename IX> static void twin_one(const RgState &st, const RgMs
 }
 template <int P> static void twin_tick(const RgState &st, const RgMsgs &ms, u32 *pk, int mode) {
     const bool fits32 = rg_fits_u32_offsets(P, st.stride);
+    twin_wave_mode = mode == 3;
+    if (mode == 3) mode = 2;
     for (u64 g = 0; g < st.G; g++) { // (odd groups with 64-bit indices: both index types of the loader are compared)
+        if (twin_wave_mode && !(g & 63u)) { // the block's answer, from the plane as the last tick left it
+            twin_wave_any = false;
+            for (u64 k = g; k < g + 64 && k < st.G; k++)
+                for (int p = 0; p < P; p++) {
+                    const u32 w = pk[(u64)p * st.stride + k];
+                    twin_wave_any = twin_wave_any || (w & 0xffffu) == RG_MIRROR_MT_ESC || (w >> 16) == RG_MIRROR_PC_ESC;
+                }
+        }
         if (fits32 && !(g & 1)) twin_one<P, u32>(st, ms, pk, mode, (u32)g);
         else twin_one<P, u64>(st, ms, pk, mode, g);
     }
+    twin_wave_mode = false;
 }
 
 extern "C" int rg_mirror_twin_tick(unsigned P, unsigned long G, unsigned long stride, void *const *state, const void *const *msg,

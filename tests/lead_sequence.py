@@ -53,6 +53,13 @@ MF_BECOME_LEADER, OUT_TIMEOUT_NOW = 0x02, 0x4
 CASES = [(3, False, 1), (3, True, 8), (5, False, 8), (5, True, 1), (8, False, 4), (5, False, 0)]
 SEEDS = {(3, False, 1): 2, (3, True, 8): 2, (5, False, 8): 3, (5, True, 1): 2, (8, False, 4): 1, (5, False, 0): 1}
 TWIN_CASE, TWIN_SEED = (5, False, 8), 2
+# (P, seed) of the read-mirror sequences (tests/test_lead_sequences_gpu.py): max_inflight 0, 32-bit offsets, no size classes, the
+# chooser with tick_runs -- runs of 2-4 consecutive plain ticks, so that the dense tick finds its plane valid (packed launches)
+# Seeds with fewer than RG_MIRROR_WINDOW = 32 mirror launches in all: the engine's escape watch never takes a look. (It would switch
+# the mirror off on this stream, rightly: half of fuzz.random_msgs' acks carry Message.commit = commit + 1, a committed_index ABOVE
+# the commit index, which the packed word cannot hold, so most waves store an escape.)
+MIRROR_CASES = [(3, 1), (5, 5)]
+MIRROR_LAUNCHES = {(3, 1): (11, 19), (5, 5): (10, 20)}  # (build, packed) launches of the mirror-on engine: floors of the seeds
 
 DECK = (["tick_one"] * 3 + ["tick_two"] * 3 + ["gated_one"] * 2 + ["gated_two"] * 2 + ["reelect"] * 3 + ["clock"] * 9 + ["conf_dense"] * 3 +
         ["conf_sparse"] * 2 + ["transfer_dense"] * 3 + ["transfer_sparse"] * 2 + ["events_records"] * 2 + ["events_dense"] * 2 +
@@ -494,9 +501,14 @@ class Chooser:
     precondition the state does not meet yet waits for a later step. twin: only inputs BOTH forms of a call take (no malformed word,
     no slot at or beyond P), for the test that runs the dense and the sparse forms side by side."""
 
-    def __init__(self, seed, P, cap, G=G_DEFAULT, twin=False):
+    def __init__(self, seed, P, cap, G=G_DEFAULT, twin=False, tick_runs=False):
+        """tick_runs: every plain tick of the deck is followed by 1-3 more plain ticks (op["follows"] on them), and every ungated
+        tick carries op["columns_only"]: whoever runs beside the truth reads nothing but columns behind it, so the next op -- a
+        tick of the run, or whatever call the deck holds next -- finds the engine as the tick left it. The default draws exactly
+        what it always drew."""
         self.rng = np.random.default_rng(9100 + seed)
         self.P, self.cap, self.G, self.twin = P, cap, G, twin
+        self.tick_runs, self.run_left = tick_runs, 0
         self.deck = [DECK[i] for i in self.rng.permutation(len(DECK))]
         # the first two steps, while every group is still led, over workgroups 0 and 1 as shape_workgroups prepared them: a dense
         # transfer in which every lane of workgroup 1 owes its item (workgroup 0 names its own leader: SELF, nothing moves), then a
@@ -515,7 +527,16 @@ class Chooser:
             return "clock" in self.deck and len(tr.stopped_groups()) > 0
         return True
 
+    def done(self):
+        return not self.deck and not self.run_left
+
     def next(self, tr):
+        if self.run_left:  # (tick_runs: the rest of a run of plain ticks)
+            self.run_left -= 1
+            op = self._tick(tr, "tick_one" if self.rng.random() < 0.5 else "tick_two")
+            op.update(name="tick_one" if op["launches"] == 1 else "tick_two", bad=None, follows=True, columns_only=True)
+            self.step += 1
+            return op
         name = next((n for n in self.deck if self.ready(n, tr)), None)
         if name is None:  # (nothing is ready: the first op in the form the state allows)
             name = self.deck[0]
@@ -531,6 +552,9 @@ class Chooser:
             name = "tick_one" if op["launches"] == 1 else "tick_two"
         op["name"] = name
         op["bad"] = self.bad_call(tr, op)
+        if self.tick_runs and op["kind"] == "tick" and op["terms"] is None:
+            self.run_left = int(self.rng.integers(1, 4))
+            op["columns_only"] = True
         self.step += 1
         return op
 
@@ -681,6 +705,24 @@ class Chooser:
             return None
         self.bad_order.append(self.bad_order.pop(0))  # (in turn, from a start the seed sets: no call is drawn twice before all were)
         return {"call": self.bad_order[-1], "when": "before", "group": int(rng.integers(0, self.G))}
+
+
+def mirror_classes(op, first=False):
+    """What one step of tests/test_lead_sequences_gpu.py's Runner does to the dense tick's read mirror, as call classes of
+    readmirror.after, in order: the load and the first check drop it; a forbidden call is tried between two reads of the whole
+    engine (rg_read_groups: drop); a gated tick enters through rgt_lead_gate_device first; every other op but the tick drops;
+    the check behind a step reads the clock cells (drop) unless the op says columns only (an ungated tick under tick_runs: keep)."""
+    classes = ["drop"] if first else []
+    if op["bad"]:
+        classes.append("drop")
+    if op["kind"] == "tick":
+        if op["terms"] is not None:
+            classes.append("drop")
+        classes.append("tick")
+    else:
+        classes.append("drop")
+    classes.append("keep" if op.get("columns_only") else "drop")
+    return classes
 
 
 def sequence(seed, P, cap, G=G_DEFAULT, twin=False, steps=STEPS):

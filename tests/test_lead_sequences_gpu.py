@@ -44,12 +44,15 @@ class Runner:
     """One engine beside the truth. form: None = every call in the form its op names; "dense" / "sparse" = that form wherever an op has
     two (a tick: one launch / two launches) -- the twins."""
 
-    def __init__(self, rg, tr, ix64, form=None):
+    def __init__(self, rg, tr, ix64, form=None, flags=None):
+        """flags: more RG_CFGF_* bits for the engine (the read-mirror cases: NO_SIZE_CLASSES, NO_READ_MIRROR)"""
         import torch
         self.rg, self.E, self.torch, self.tr, self.form = rg, rg.engine, torch, tr, form
         self.G, self.P, self.cap = tr.G, tr.P, tr.cap
         E = self.E
-        self.eng = eng = rg.Engine(self.G, self.P, flags=E.CFGF.IX64 if ix64 else None, max_inflight=self.cap)
+        if flags is not None:
+            flags |= E.CFGF.IX64 if ix64 else 0
+        self.eng = eng = rg.Engine(self.G, self.P, flags=(E.CFGF.IX64 if ix64 else None) if flags is None else flags, max_inflight=self.cap)
         assert eng.stride == tr.stride
         self.stride = eng.stride
         for k in LOAD_COLS:
@@ -98,11 +101,15 @@ class Runner:
         return (self.eng.read_groups(self.everyone).tobytes(), [a.tobytes() for a in self.eng.read_inflights()] if self.cap else None,
                 self.eng.lead_clock_read(self.everyone).tobytes())
 
-    def check_state(self):
+    def check_state(self, columns_only=False):
+        """columns_only: rg_read_column alone, which keeps the dense tick's read mirror (the clock cells are read through an entry
+        point that drops it) -- between the ticks of a run (lead_sequence.Chooser tick_runs)"""
         tr = self.tr
         d = S.first_diff(tr.st, self.read())
         if d:
             self.fail("column", *d)
+        if columns_only:
+            return
         if self.cap:
             d = S.first_window_diff(tr.win, tr.st, self.cap, *self.windows())
             if d:
@@ -144,7 +151,7 @@ class Runner:
         if op["bad"] and op["bad"]["when"] == "before":
             self.bad_call(op["bad"])
         getattr(self, "_" + op["kind"])(op, want, form in ("dense", "one launch"))
-        self.check_state()
+        self.check_state(columns_only=bool(op.get("columns_only")))
 
     def check_gate(self, want, got_rows, in_rows, flags, events, new_term, down, counts, alias):
         G = self.G
@@ -395,3 +402,47 @@ def test_dense_and_sparse_twins_stay_byte_equal(rg):
     finally:
         a.close()
         b.close()
+
+
+@pytest.mark.parametrize("P,seed", S.MIRROR_CASES)
+def test_sequences_with_packed_launches_match_the_model_and_a_mirror_less_twin(rg, P, seed):
+    """max_inflight 0, 32-bit offsets, no size classes: the engines whose dense tick is k_tick_mirror. One engine with the read
+    mirror, one created with RG_CFGF_NO_READ_MIRROR, the same model, never refreshed from either. The chooser emits runs of 2-4
+    plain ticks behind which only columns are read, so ticks find their plane valid -- and so does the call behind a run, which
+    has to drop it. After every step both engines equal the
+    model; after every step with a full check their images are byte-equal; and rgr_mirror_stats is what readmirror.after predicts
+    from the op sequence alone -- build and packed launches and the flag, after every step."""
+    import readmirror as RM
+    E = rg.engine
+    tr, ch = S.Truth(seed, P, 0), S.Chooser(seed, P, 0, tick_runs=True)
+    on = Runner(rg, tr, False, flags=E.CFGF.NO_SIZE_CLASSES)
+    off = Runner(rg, tr, False, flags=E.CFGF.NO_SIZE_CLASSES | E.CFGF.NO_READ_MIRROR)
+    try:
+        assert on.eng.mirror_stats()["present"] == 1 and off.eng.mirror_stats()["present"] == 0
+        for run in (on, off):
+            run.where = (seed, -1, "load", "-")
+            run.check_state()
+        build = packed = step = 0
+        valid = False
+        while not ch.done():
+            op = ch.next(tr)
+            want = tr.apply(op)
+            for run in (on, off):
+                run.apply(seed, step, op, want)
+            build, packed, valid = RM.launch_counts(S.mirror_classes(op, first=step == 0), valid, build, packed)
+            s = on.eng.mirror_stats()
+            assert (s["build_launches"], s["packed_launches"], s["valid"], s["off"]) == (build, packed, int(valid), 0), (seed, step, op["name"], s, build, packed, valid)
+            s = off.eng.mirror_stats()
+            assert (s["build_launches"], s["packed_launches"], s["valid"]) == (0, 0, 0), s
+            if op["kind"] == "tick":
+                info = on.eng.device_info()
+                assert info["last_tick_kernel"] == rg.KERNEL.NAMES[rg.KERNEL.LANE] and info["last_tick_offset_bits"] == 32, info
+            if not op.get("columns_only"):  # (the images are read through entry points that drop the mirror: not behind a plain tick)
+                for what, x, y in zip(("rg_read_groups", "the Inflights dump", "the clock cells"), on.image(), off.image()):
+                    assert x == y, "seed %d step %d op %s: %s of the mirror engine and its twin differ" % (seed, step, op["name"], what)
+            step += 1
+        assert (build, packed) == S.MIRROR_LAUNCHES[(P, seed)], (build, packed)
+        S.check_floors(tr.cov, 0)
+    finally:
+        on.close()
+        off.close()

@@ -215,3 +215,28 @@ def test_each_mutation_of_the_continuous_executor_is_caught(oracle, mutation):
     assert len(caught) == 3 and all(c[2].startswith(want[0]) and c[3][0] == want[1] for c in caught), caught
     assert mutation != "added_peer_not_recent_active" or all(c[3][1] == "pflags" for c in caught)
     assert mutation != "step_down_keeps_transferee" or all(c[3][1] == "cfg" for c in caught)
+
+
+@pytest.mark.parametrize("P,seed", S.MIRROR_CASES)
+def test_the_read_mirror_seeds_meet_their_floors_and_produce_packed_launches(oracle, P, seed):
+    """The seeds of the read-mirror sequences (tick_runs: runs of 2-4 plain ticks), on the model alone: the floors of every
+    sequence, and what readmirror.after predicts for the engine beside it -- packed launches, i.e. ticks that read the plane."""
+    import readmirror as RM
+    tr, ch = S.Truth(seed, P, 0), S.Chooser(seed, P, 0, tick_runs=True)
+    classes, runs, dropped_valid, valid = [], [], 0, False
+    while not ch.done():
+        op = ch.next(tr)
+        tr.apply(op)
+        step = S.mirror_classes(op, first=not classes)
+        dropped_valid += valid and step[0] == "drop"  # a call that has to drop a plane a tick left valid
+        classes += step
+        valid = RM.launch_counts(classes)[2]
+        if op["kind"] == "tick" and not op.get("follows"):
+            runs.append(1)
+        elif op.get("follows"):
+            runs[-1] += 1
+    S.check_floors(tr.cov, 0)
+    build, packed, valid = RM.launch_counts(classes)
+    assert (build, packed) == S.MIRROR_LAUNCHES[(P, seed)] and packed >= 15 and build + packed < 32, (build, packed)
+    assert {2, 3, 4} >= {r for r in runs if r > 1} and max(runs) >= 3, runs
+    assert dropped_valid >= 5, dropped_valid

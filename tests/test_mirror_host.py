@@ -3,7 +3,10 @@
 (1) the packed word at its edges; (2) two roads over one random stream -- (a) rg_load_group / tick / rg_store_group, (b) build once,
 then packed -- leave every column and every result word equal after every tick, and every field of the plane that is not the escape
 decodes to its column cell; (3) the share of escaped fields on the benchmark's stream; (4) the rgr_* exports are the header's, bound
-and generated."""
+and generated; (5) the same roads with the twin's WAVE mode, in which a block of 64 groups takes the escape branch together as
+the wave does on the device, and ONE escaping lane in a steady wave (readmirror.plant_wave) in both modes; (6) a word wrong by
+one, in the slot that decides the commit index or in an acker's committed_index, shows in the columns: the packed tick computes
+on the plane. The helpers shared with the GPU tests live in tests/readmirror.py."""
 import ctypes as C
 import copy
 import os
@@ -16,6 +19,8 @@ import pytest
 
 import fuzz
 import oracle_lib as O
+from readmirror import (EDGES, KINDS, M64, MT_ESC, PC_ESC, check_plane, deciding_acks, model_word, new_plane, plant_edges,
+                        plant_wave, wave_groups)
 from test_host_check import msg_ptrs, state_ptrs
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -23,8 +28,6 @@ ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "host_check", "mirror_twin.hip")
 LIB = os.path.join(HERE, "host_check", "libmirror_twin.so")
 CSRC = os.path.join(ROOT, "raft_rs_amd", "csrc")
-MT_ESC, PC_ESC = 0x8000, 0xFFFF
-M64 = (1 << 64) - 1
 
 
 @pytest.fixture(scope="module")
@@ -46,17 +49,6 @@ def twin():
     return L
 
 
-def model_word(mt, pc, c):
-    """The issue's definition, in Python integers: differences in 64-bit wrap-around arithmetic, then range-checked."""
-    dm = (mt - c) & M64
-    sm = dm - (1 << 64) if dm >> 63 else dm
-    lo = (sm & 0xFFFF) if -32767 <= sm <= 32767 else MT_ESC
-    dp = (c - pc) & M64
-    hi = dp if dp <= 65534 else PC_ESC
-    return lo | (hi << 16)
-
-
-EDGES = (0, 1, 32766, 32767, 32768, 65534, 65535, 65536)
 BASES = (0, 1, 70000, (1 << 32) - 1, 1 << 32, (1 << 32) + 70000, (1 << 63) - 1, 1 << 63, M64 - 1, M64)
 
 
@@ -85,63 +77,19 @@ def test_word_edges(twin):
     assert twin.rg_mirror_twin_encode(100000, 100001, 100000) >> 16 == PC_ESC  # committed_index above commit
 
 
-def new_plane(st):
-    return np.full((st["n_slots"], st["stride"]), 0xDEADBEEF, dtype=np.uint32)  # (never read before a build tick wrote it)
-
-
 def run(twin, st, msgs, out, pk, mode):
     rc = twin.rg_mirror_twin_tick(st["n_slots"], st["n_groups"], st["stride"], state_ptrs(st, out), msg_ptrs(msgs),
                                   pk.ctypes.data if pk is not None else None, mode)
     assert rc == 0
 
 
-def check_plane(st, pk):
-    """Wherever a field is not the escape the decoded word is the column cell; a slot WITHOUT a Progress holds the word 0 and never
-    an escape (no tick looks at what it decodes to). -> (fields, escaped fields, blocks of 64 groups = waves that hold an escape)"""
-    G, P = st["n_groups"], st["n_slots"]
-    c = st["commit"][:G]
-    present = (st["cfg"][:G] >> 24) & 0xFF
-    esc = 0
-    group_esc = np.zeros(G, dtype=bool)
-    for p in range(P):
-        w = pk[p, :G].astype(np.uint64)
-        lo, hi = w & np.uint64(0xFFFF), w >> np.uint64(16)
-        sext = np.where(lo >= 0x8000, lo.astype(np.int64) - 65536, lo.astype(np.int64)).astype(np.uint64)
-        dec_mt, dec_pc = c + sext, c - hi  # (uint64 arithmetic wraps)
-        has = ((present >> p) & 1).astype(bool)
-        assert (w[~has] == 0).all(), (p, np.nonzero(~has & (w != 0))[0][:5])
-        ok_mt = ~has | (lo == MT_ESC) | (dec_mt == st["match"][p, :G])
-        ok_pc = ~has | (hi == PC_ESC) | (dec_pc == st["pr_commit"][p, :G])
-        assert ok_mt.all(), (p, np.nonzero(~ok_mt)[0][:5])
-        assert ok_pc.all(), (p, np.nonzero(~ok_pc)[0][:5])
-        esc += int((lo == MT_ESC).sum()) + int((hi == PC_ESC).sum())
-        group_esc |= (lo == MT_ESC) | (hi == PC_ESC)
-    waves = sum(int(group_esc[b:b + 64].any()) for b in range(0, G, 64))
-    return 2 * P * G, esc, waves
-
-
-def plant_edges(rng, st, groups):
-    """Groups whose cells sit at the edges of the word: match = commit +- EDGES, committed_index commit - EDGES and ABOVE commit,
-    commits at 0, 2^32 - 1, 2^32 and 2^63 - 1 (wrap-around on either side)."""
-    P = st["n_slots"]
-    commits = [0, 5, (1 << 32) - 1, 1 << 32, (1 << 63) - 1, 3_000_000, 40_000, 65_535]
-    for i, g in enumerate(groups):
-        c = commits[i % len(commits)]
-        st["commit"][g] = c
-        hi = max(c, 1) + 70_000 if c < (1 << 62) else c  # last_index at or beyond everything planted below
-        st["term_hi"][g] = min(hi, M64)
-        st["term_lo"][g] = max(1, c - 3) if c else 1
-        for p in range(P):
-            d = EDGES[(i // len(commits) + p) % len(EDGES)]
-            s = 1 if (i + p) & 1 else -1
-            st["match"][p, g] = (c + s * d) & M64
-            st["next"][p, g] = (int(st["match"][p, g]) + 1) & M64
-            e = EDGES[(i + 2 * p) % len(EDGES)]
-            st["pr_commit"][p, g] = (c - e) & M64 if (i + p) % 5 else (c + 1 + e) & M64  # every fifth: above commit
-
-
 @pytest.mark.parametrize("P", [1, 3, 5, 7, 8])
 def test_packed_road_equals_plain_road(twin, P):
+    packed_road_equals_plain_road(twin, P, 2)
+
+
+def packed_road_equals_plain_road(twin, P, packed_mode):
+    """packed_mode 2: every lane decides the escape branch for itself; 3: the block of 64 groups does (the device's wave)."""
     G, T, term = 257, 12, 5
     rng = np.random.default_rng(0xA11CE + P)
     a = O.add_term_table(O.alloc_state(G, P))
@@ -174,7 +122,7 @@ def test_packed_road_equals_plain_road(twin, P):
         if planted:  # the planted groups sit this tick out, so that the build tick encodes the planted cells themselves
             msgs["m_flags"][edge_groups, :] = 0
         run(twin, a, msgs, out_a, None, 0)
-        run(twin, b, msgs, out_b, pk, 1 if planted else 2)
+        run(twin, b, msgs, out_b, pk, 1 if planted else packed_mode)
         diffs = fuzz.diff_states(a, b, G, P, present_only=False)
         assert not diffs, (t, diffs[:5])
         assert (out_a == out_b).all(), (t, np.nonzero(out_a != out_b)[0][:5])
@@ -264,3 +212,185 @@ def test_mirror_export_is_the_headers(rg):
     info = E.MirrorInfo()
     assert lib.rgr_mirror_stats_fn(None, C.byref(info)) == -1 and b"rgr_mirror_stats" in lib.rg_last_error()
     assert int(re.search(r"#define RGR_MIRROR_VERSION (\d+)u", hdr).group(1)) == E.MIRROR_VERSION
+
+
+# ---- the device's wave semantics on the twin; one escaping lane; the comparison reads the plane ------------------------------
+@pytest.mark.parametrize("P", [1, 3, 5, 7, 8])
+def test_packed_road_equals_plain_road_decided_by_the_wave(twin, P):
+    """The same two roads with the twin's WAVE mode: a block of 64 consecutive groups takes the escape branch of rg_load_group_pk
+    together, as the wave does on the device (a lane without an escape then re-reads its cells because a neighbour has one)."""
+    packed_road_equals_plain_road(twin, P, 3)
+
+
+def steady_shard(rng, G, P, term):
+    """Every wave steady (readmirror.plant_wave): the state the one-lane and the corrupted-plane tests start from."""
+    st = O.add_term_table(O.alloc_state(G, P))
+    st["cfg"][:] = fuzz.random_cfg(rng, G, P, transfer_frac=0.0)
+    fuzz.random_state(rng, st)
+    for w in range((G + 63) // 64):
+        plant_wave(st, w, (), "mt_hi")
+    fuzz.random_term_table(rng, st, term, max_runs=4)
+    return st
+
+
+def silence(msgs):
+    msgs["m_flags"][...] = 0
+    return msgs
+
+
+@pytest.mark.parametrize("packed_mode", [2, 3])
+@pytest.mark.parametrize("kind", sorted(KINDS))
+@pytest.mark.parametrize("P", [3, 5, 7])
+def test_one_escaping_lane_in_a_steady_wave(twin, P, kind, packed_mode):
+    """plant_wave: lanes {0}, {31}, {63}, {0, 63} of the first, a middle and the (partial) tail wave hold one escaping field, every
+    other group of the shard is steady. Build tick without messages, a packed tick in which a silent voter's cell decides the
+    commit index of every group of the planted wave and of one steady wave, two random ticks -- against the plain road."""
+    term = 5
+    for G, wave, lanes in ((257 + 64, 0, (0,)), (257 + 64, 2, (31,)), (257 + 64, 5, (0,)), (129, 1, (63,)), (129, 2, (0,)),
+                           (65, 1, (0,)), (63, 0, (0, 62)), (257 + 64, 3, (0, 63)), (1, 0, (0,)), (63, 0, (31,)), (100, 1, (31,)), (100, 1, (0, 35)),
+                           (128, 1, (0, 63)), (128, 1, (63,)), (257 + 64, 0, (0, 63))):
+        rng = np.random.default_rng(G * 100 + wave * 10 + P)
+        a = steady_shard(rng, G, P, term)
+        planted = plant_wave(a, wave, lanes, kind)
+        assert len(planted) == len(lanes)
+        b = copy.deepcopy(a)
+        pk = new_plane(b)
+        msgs = silence(O.alloc_msgs(G, P))
+        out_a, out_b = np.zeros(G, dtype=np.uint32), np.zeros(G, dtype=np.uint32)
+        steady = (wave + 1) % ((G + 63) // 64)
+        decided = 0
+        for t in range(4):
+            if t == 1:
+                listed = sorted(set(wave_groups(a, wave)) | set(wave_groups(a, steady)))
+                decided = len(deciding_acks(a, msgs, listed))
+                before = a["commit"].copy()
+            elif t > 1:
+                fuzz.random_msgs(rng, a, msgs, elect_p=0.05, elect_term=term + t, reject_p=0.2)
+            run(twin, a, msgs, out_a, None, 0)
+            run(twin, b, msgs, out_b, pk, 1 if t == 0 else packed_mode)
+            diffs = fuzz.diff_states(a, b, G, P, present_only=False)
+            assert not diffs, (G, wave, lanes, t, diffs[:5])
+            assert (out_a == out_b).all(), (G, wave, lanes, t)
+            _, esc, waves = check_plane(b, pk)
+            if t == 0:  # exactly the planted fields escape, in exactly one wave
+                assert (esc, waves) == (len(lanes), 1), (G, wave, lanes, esc, waves)
+                for g, p in planted:
+                    w = int(pk[p, g])
+                    assert ((w & 0xFFFF) == MT_ESC) != ((w >> 16) == PC_ESC)
+            if t == 1:
+                moved = int((a["commit"] > before).sum())
+                assert moved == decided and (decided >= len(listed) // 4 or G == 1), (G, wave, decided, len(listed))
+
+
+def corrupt(pk, cells, field, delta):
+    """delta added to the low (0) or high (1) field of the listed (group, slot) words, where neither the old nor the new field
+    is the escape and the field does not wrap. -> the cells that were changed."""
+    done = []
+    for g, s in cells:
+        w = int(pk[s, g])
+        lo, hi = w & 0xFFFF, w >> 16
+        if field == 0:
+            new = (lo + delta) & 0xFFFF
+            if MT_ESC in (lo, new):
+                continue
+            pk[s, g] = new | (hi << 16)
+        else:
+            new = hi + delta
+            if PC_ESC in (hi, new) or not 0 <= new < PC_ESC:
+                continue
+            pk[s, g] = lo | (new << 16)
+        done.append((g, s))
+    return done
+
+
+def groups_that_differ(a, b, G, P):
+    bad = np.zeros(G, dtype=bool)
+    for k in fuzz.STATE_KEYS:
+        x, y = a[k], b[k]
+        if k == "pflags":
+            bad |= (x[:G, :P] != y[:G, :P]).any(axis=1)
+        elif x.ndim == 2:
+            bad |= (x[:P, :G] != y[:P, :G]).any(axis=0)
+        else:
+            bad |= x[:G] != y[:G]
+    return bad
+
+
+@pytest.mark.parametrize("packed_mode", [2, 3])
+@pytest.mark.parametrize("P", [2, 3, 5, 7, 8])
+def test_a_corrupted_word_changes_what_the_tick_commits(twin, P, packed_mode):
+    """The packed tick COMPUTES on the plane: after a build tick, the word of the slot whose `matched` decides the commit index
+    (readmirror.deciding_acks) gets 1 added to, or taken from, its low field in half of the groups. Every such group then
+    commits something else than the plain road, no other group differs in any column. This is what makes a comparison of a
+    packed tick under deciding_acks meaningful: a wrongly decoded cell of a silent slot shows in `commit`."""
+    G, term = 257, 5
+    for delta in (1, -1):
+        rng = np.random.default_rng(0xC0 + P)
+        a = steady_shard(rng, G, P, term)
+        b = copy.deepcopy(a)
+        pk = new_plane(b)
+        msgs = silence(O.alloc_msgs(G, P))
+        out_a, out_b = np.zeros(G, dtype=np.uint32), np.zeros(G, dtype=np.uint32)
+        run(twin, a, msgs, out_a, None, 0)
+        run(twin, b, msgs, out_b, pk, 1)
+        decided = deciding_acks(a, msgs, range(G))
+        assert len(decided) >= G // 8, len(decided)  # (a floor on the construction: at two slots most groups have ONE voter)
+        hit = corrupt(pk, decided[::2], 0, delta)
+        assert len(hit) == len(decided[::2])  # (steady cells: no field near the escape)
+        run(twin, a, msgs, out_a, None, 0)
+        run(twin, b, msgs, out_b, pk, packed_mode)
+        bad = groups_that_differ(a, b, G, P)
+        hit_g = np.zeros(G, dtype=bool)
+        hit_g[[g for g, _ in hit]] = True
+        assert (a["commit"][hit_g] != b["commit"][hit_g]).all(), np.nonzero(hit_g & (a["commit"] == b["commit"]))[0][:5]
+        assert not (bad & ~hit_g).any(), np.nonzero(bad & ~hit_g)[0][:5]
+        assert (a["commit"][[g for g, _ in decided]] == [a["match"][s, g] for g, s in decided]).all()
+
+
+@pytest.mark.parametrize("packed_mode", [2, 3])
+@pytest.mark.parametrize("P", [2, 3, 5, 7, 8])
+def test_a_corrupted_committed_index_reaches_its_column(twin, P, packed_mode):
+    """The high field (commit - committed_index), in the words of the ACKERS of deciding_acks, 1 taken from it or added to it in
+    half of the groups.
+
+    Observable, and asserted for every corrupted cell and no other: the acks carry a Message.commit that is not above the
+    acker's committed_index (0). Progress::update_committed then changes nothing, and since the tick rewrites the cells of every
+    slot that had an event from its registers (RG_OPT_UNCOND_ST, the default build: whole lines instead of lane-masked stores),
+    the decoded value itself lands in RG_COL_PR_COMMIT: one above or one below the plain road's cell.
+
+    UNOBSERVABLE by the tick's arithmetic, named here and asserted as such so that the claim is checked rather than believed:
+    the construction with Message.commit exactly one above the true committed_index. Decoded one higher, update_committed finds
+    nothing to do -- but the store is NOT skipped, the slot had an event and is rewritten unconditionally with the decoded value,
+    which is Message.commit, the right value. Decoded one lower, update_committed is a maximum and stores Message.commit. More
+    generally a wrong committed_index below Message.commit never shows, and one of a slot WITHOUT an event is neither compared
+    with anything nor stored (the leader's own cell is raised to the new commit index, which is above every representable
+    committed_index): only a slot with an event whose Message.commit does not cover the error carries it into the column."""
+    G, term = 257, 5
+    for delta, above in ((-1, False), (1, False), (-1, True), (1, True)):
+        rng = np.random.default_rng(0xC1 + P)
+        a = steady_shard(rng, G, P, term)
+        b = copy.deepcopy(a)
+        pk = new_plane(b)
+        msgs = silence(O.alloc_msgs(G, P))
+        out_a, out_b = np.zeros(G, dtype=np.uint32), np.zeros(G, dtype=np.uint32)
+        run(twin, a, msgs, out_a, None, 0)
+        run(twin, b, msgs, out_b, pk, 1)
+        decided = deciding_acks(a, msgs, range(G), m_commit_above=above)
+        assert len(decided) >= G // 8
+        ackers = [(g, s) for g, _ in decided[::2] for s in range(P) if msgs["m_flags"][g, s]]
+        hit = corrupt(pk, ackers, 1, delta)
+        assert len(hit) >= (3 * len(ackers)) // 4  # (committed_index == commit, field 0, cannot be reduced: 1 cell in 201)
+        run(twin, a, msgs, out_a, None, 0)
+        run(twin, b, msgs, out_b, pk, packed_mode)
+        cell = np.zeros((P, a["stride"]), dtype=bool)
+        for g, s in hit:
+            cell[s, g] = True
+        differs = a["pr_commit"] != b["pr_commit"]
+        if above:
+            assert not differs.any(), (delta, np.argwhere(differs)[:5])
+        else:
+            assert (differs == cell).all(), (delta, np.argwhere(differs != cell)[:5])
+            assert all(int(b["pr_commit"][s, g]) == int(a["pr_commit"][s, g]) - delta for g, s in hit)
+        a["pr_commit"][cell] = b["pr_commit"][cell]
+        assert not fuzz.diff_states(a, b, G, P, present_only=False)
+        assert (out_a == out_b).all()
