@@ -16,13 +16,19 @@
  * which the tick loads anyway. An engine that can run that kernel (lane variant, 32-bit cell offsets, max_inflight == 0, no
  * RG_CFGF_NO_READ_MIRROR) therefore keeps, next to its columns, one packed 32-bit word per slot and group (4 x n_slots x stride
  * bytes, counted in rg_device_info.engine_bytes): the tick writes it behind its ordinary stores, and the NEXT dense tick reads it in
- * the place of the two cells. The columns are written exactly as without it and are correct after every call; the plane is no
- * RG_COL_*, is reachable through no column call and is part of no checkpoint.
+ * the place of the two cells. Through every call that looks at them the columns hold exactly what they hold without the mirror; the
+ * plane is no RG_COL_*, is reachable through no column call and is part of no checkpoint.
  *
  * The plane is a cache, and its one protocol is invalidation: every entry point that takes the engine drops it, except the dense
  * tick itself and the calls that write none of the three columns (rg_results, rg_result_counts, rg_sync, rg_get_device_info,
  * rg_msg_stats, rg_read_column, rg_workload_gen, and this header's). A tick that finds it dropped reads the columns as ever and rebuilds it (a
  * "build" launch: 4 B per slot and group more than a tick without the mirror); a tick that finds it valid is a "packed" launch.
+ * WRITE-BEHIND. Once packed launches follow one another with nothing but such calls in between, the packed launch stops storing
+ * the RG_COL_MATCH / RG_COL_PR_COMMIT cells the words stand for (the plane is then the state of the two columns, not their cache),
+ * and the engine writes them back from the plane before anything reads or writes them or ends the streak: every entry point that
+ * drops the plane, rg_read_column of one of the two, rg_workload_gen, rg_column_ptr, and any dense tick on another kernel. The
+ * dense tick itself, rg_results, rg_result_counts, rg_sync, rg_get_device_info, rg_msg_stats, rg_read_column of other columns and
+ * this header's call do not. Nothing of it shows through the ABI: packed_launches counts both kinds of packed launch.
  * The mirror stays off while a resident mailbox workgroup runs (rg_mailbox_start), and for good once rg_column_ptr has handed
  * out RG_COL_MATCH, RG_COL_PR_COMMIT or RG_COL_COMMIT or a tick has been captured into a graph (whoever holds the pointer or the
  * graph changes the columns without an entry point). rg_device_info.last_tick_kernel / last_tick_streaming report what they

@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG, "csrc")
 OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "libraftgroups.so")
 UNITS = ["abi_state.hip", "abi_tick.hip", "abi_send.hip", "abi_mirror.hip", "abi_wire.hip", "abi_publish.hip", "abi_placement.hip", "abi_read.hip", "abi_follow.hip", "abi_elect.hip", "abi_handoff.hip", "ext_lead.hip", "ext_term.hip", "ext_vote.hip", "ext_handoff.hip", "ext_conf.hip", "ext_transfer.hip", "ext_mirror.hip"]
-DEPS = UNITS + ["tick_inst.hip", "rg_engine.h", "rg_grow.h", "rg_runs.h", "rg_abi_guard.h", "rg_common.h", "rg_group.h", "rg_send.h", "rg_wire.h", "rg_workload.h", "rg_tick_kernels.h", "rg_mirror.h",
+DEPS = UNITS + ["tick_inst.hip", "rg_engine.h", "rg_grow.h", "rg_runs.h", "rg_abi_guard.h", "rg_common.h", "rg_group.h", "rg_send.h", "rg_wire.h", "rg_workload.h", "rg_tick_kernels.h", "rg_mirror.h", "rg_mirror_host.h",
                 "rg_publish.h", "rg_kernels_quorum.h", "rg_kernels_sparse.h", "rg_kernels_send.h", "rg_kernels_state.h",
                 "rg_kernels_workload.h", "rg_kernels_publish.h", "rg_kernels_placement.h", "rg_read.h", "rg_kernels_read.h", "rg_follow.h", "rg_kernels_follow.h", "rg_elect.h", "rg_kernels_elect.h", "rg_handoff.h", "rg_kernels_handoff.h", "rg_handoff_host.h", "rg_wave.h", "rg_lead.h", "rg_kernels_lead.h", "rg_term.h", "rg_kernels_term.h", "rg_vote.h", "rg_kernels_vote.h", "rg_promote.h", "rg_kernels_promote.h", "rg_conf.h", "rg_kernels_conf.h", "rg_transfer.h", "rg_kernels_transfer.h", os.path.join("..", "..", "include", "raftgroups.h"),
                 os.path.join("..", "..", "include", "raftgroups_lead.h"), os.path.join("..", "..", "include", "raftgroups_term.h"), os.path.join("..", "..", "include", "raftgroups_vote.h"),

@@ -670,7 +670,9 @@ static int rg_flush_collect(rg_engine *h, const RgSendReq *send, const RgFlushRu
 static int rg_sparse_roundtrip(rg_engine *h, const rg_wire_msg *recs, u64 n, bool any_logterm, u32 *dup_out,
                                const RgSendReq *send = nullptr) {
     RG_HIP(hipSetDevice(h->cfg.device)); // (not RG_ENTER: this is the one path the resident mailbox kernel serves)
-    h->mirror_valid = false;             // (... so the read mirror of the dense tick is dropped here: the listed groups' cells change)
+    const int src = rg_mirror_settle(h, RG_MC_DROP); // (... so the read mirror of the dense tick is dropped here: the listed groups' cells
+    if (src) return src;                              //  change -- behind the settle, where write-behind launches left the columns stale)
+    h->mirror_valid = false;
     int rc;
     if (h->ins_arena && h->hint_check_due) { // (rare: a log-term tick came before; the check needs the stream to itself)
         rc = rg_mailbox_quiesce(h);

@@ -516,6 +516,10 @@ extern "C" int rg_read_column(rg_engine *h, int c, void *dst, uint64_t bytes) tr
         return rg_fail(RG_ERR_INVALID_ARG, "rg_read_column(%d): %llu bytes given, %llu expected", c,
                        (unsigned long long)bytes, (unsigned long long)rg_column_bytes(h, c));
     RG_ENTER_KEEP(h); // (a copy out of the arena: the read mirror stays)
+    if (c == RG_COL_MATCH || c == RG_COL_PR_COMMIT) { // ... the two columns write-behind launches leave behind the plane: settled first
+        const int src = rg_mirror_settle(h, RG_MC_KEEP_LOOK);
+        if (src) return src;
+    }
     RG_HIP(hipMemcpyAsync(dst, rg_col(h, c), bytes, hipMemcpyDeviceToHost, h->stream));
     RG_HIP(hipStreamSynchronize(h->stream));
     return RG_OK;
@@ -525,6 +529,7 @@ extern "C" void *rg_column_ptr(rg_engine *h, int c) {
     if (!h || c < 0 || c >= RG_COL_COUNT) return nullptr;
     if (c == RG_COL_CFG) h->cls_off = true; // whoever holds this pointer can rewrite cfg words behind the engine's back
     if (c == RG_COL_MATCH || c == RG_COL_PR_COMMIT || c == RG_COL_COMMIT) { // ... or the cells the read mirror caches
+        if (rg_mirror_settle(h, RG_MC_OFF) != RG_OK) return nullptr; // (the columns current before anybody holds the pointer)
         h->mirror_off = true;
         h->mirror_valid = false;
     }

@@ -161,7 +161,8 @@ static bool rg_lane_variant(const rg_engine *h) {
 
 // What a dense tick will run, decided before anything is launched: the kernel (RG_KERNEL_*), the width of its cell offsets and
 // its memory regime (0 = cached, 1 = message columns streamed, 2 = state columns as well) -- what rg_device_info reports.
-// mirror: the lane kernel runs as k_tick_mirror (rg_mirror.h) -- 1 = it builds the plane from the columns, 2 = it reads the plane;
+// mirror: 1 = the lane kernel runs as one of the mirror kernels (rg_mirror.h); rg_tick_impl turns it into the kernel the host state
+// asks for (RgMirrorKernel: it builds the plane from the columns, reads it, or reads it and leaves the two columns behind);
 // rg_device_info still reports RG_KERNEL_LANE and the regime: the mirror is the engine's own business (rgr_mirror_stats counts).
 struct RgTickPlan {
     u32 kernel, offset_bits, streaming, mirror;
@@ -172,6 +173,35 @@ struct RgTickPlan {
 static void rg_mirror_note_capture(rg_engine *h) {
     if (h->mirror && !h->mirror_off && rg_capturing(h, true)) h->mirror_off = true;
     if (h->mirror_off) h->mirror_valid = false;
+}
+
+// One step of the mirror's host state (rg_mirror_host.h) on the engine's three fields.
+static RgMirrorStep rg_mirror_apply(rg_engine *h, RgMirrorCall call, bool executed) {
+    RgMirrorHost m = {h->mirror_valid, h->cols_behind, h->mirror_streak};
+    const RgMirrorStep s = rg_mirror_step(m, call, RG_MIRROR_WB_AFTER_EFFECTIVE, executed);
+    h->mirror_valid = m.valid;
+    h->cols_behind = m.behind;
+    h->mirror_streak = m.streak;
+    return s;
+}
+// The settle kernel and, behind it, the memset that clears the device's "behind" word (k_tick_mirror_wb sets it; the kernel's
+// blocks return at once while it is clear). Captured into a graph the pair replays as a settle when write-behind launches ran
+// since the last one and as nothing otherwise, so the host keeps cols_behind until a settle has been EXECUTED; and a graph
+// that holds one can run behind the engine's back, so the mirror is off for good (as after any captured mirror-capable tick).
+static int rg_mirror_settle_launch(rg_engine *h, bool capturing) {
+    RG_HIP(hipSetDevice(h->cfg.device));
+    (void)h->launch->mirror(h->stream, h->st, RgMsgs(), 0, h->mirror, h->mirror_esc, RG_MK_NONE, nullptr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, "the read mirror's settle launch failed: %s", hipGetErrorString(e));
+    RG_HIP(hipMemsetAsync(h->mirror_esc.count + RG_MIRROR_BEHIND_WORD, 0, 4, h->stream));
+    if (capturing) h->mirror_off = true;
+    return RG_OK;
+}
+int rg_mirror_settle(rg_engine *h, RgMirrorCall call) {
+    if (!h->mirror) return RG_OK;
+    const bool capturing = h->cols_behind && rg_capturing(h, true);
+    const RgMirrorStep s = rg_mirror_apply(h, call, !capturing);
+    return s.settle ? rg_mirror_settle_launch(h, capturing) : RG_OK;
 }
 
 static int rg_plan_tick(rg_engine *h, bool send, RgTickPlan *plan) {
@@ -213,7 +243,7 @@ static int rg_plan_tick(rg_engine *h, bool send, RgTickPlan *plan) {
             h->mirror_win_launches = 0;
         }
         if (h->mirror_escaping) h->mirror_valid = false;
-        else if (!h->mirror_off) plan->mirror = h->mirror_valid ? 2u : 1u;
+        else if (!h->mirror_off) plan->mirror = 1u; // (which of the mirror kernels: rg_tick_impl, from the host state)
     }
     return RG_OK;
 }
@@ -249,6 +279,18 @@ int rg_tick_impl(rg_engine *h, const RgMsgs &ms, const RgSendReq *send) {
     const RgTickLaunch &go = *h->launch;
     const bool gc = h->any_group_commit;
     bool rode = false; // the event went out with the launch
+    // the read mirror's host state (rg_mirror_host.h): which mirror kernel a mirror plan runs; every other plan reads and writes
+    // the columns, and so does a build launch -- where write-behind launches left them behind the plane they are settled first
+    // (the plan that switched the mirror off -- a capture, the escape watch -- is such a plan)
+    if (h->mirror) {
+        const bool capturing = h->cols_behind && rg_capturing(h, true);
+        const RgMirrorStep ms_ = rg_mirror_apply(h, plan.mirror ? RG_MC_TICK_MIRROR : RG_MC_TICK_OTHER, !capturing);
+        if (ms_.settle) {
+            const int mrc = rg_mirror_settle_launch(h, capturing);
+            if (mrc) return mrc;
+        }
+        if (plan.mirror) plan.mirror = (u32)ms_.kernel;
+    }
     switch (plan.kernel) {
     case RG_KERNEL_TICK_SEND:
         go.tick_send(h->stream, h->st, ms, gc, h->ins, send->max_entries, send->flags, h->send_cols, plan.streaming == 2u);
@@ -262,7 +304,7 @@ int rg_tick_impl(rg_engine *h, const RgMsgs &ms, const RgSendReq *send) {
     case RG_KERNEL_SPLIT: rode = go.split(h->stream, h->st, ms, h->nt_resident, stop_evt); break;
     default: { // the lane kernel in the engine's memory regime, or the comparison kernel the engine was created with
         if (plan.mirror) { // ... with the read mirror: built from the columns, or read in their place
-            rode = go.mirror(h->stream, h->st, ms, (int)plan.streaming, h->mirror, h->mirror_esc, plan.mirror == 2u, stop_evt);
+            rode = go.mirror(h->stream, h->st, ms, (int)plan.streaming, h->mirror, h->mirror_esc, (int)plan.mirror, stop_evt);
             break;
         }
         const u32 variant = rg_lane_variant(h) ? (u32)RG_VARIANT_LANE : (u32)h->cfg.variant;
@@ -271,11 +313,12 @@ int rg_tick_impl(rg_engine *h, const RgMsgs &ms, const RgSendReq *send) {
     }
     }
     hipError_t e = hipGetLastError();
-    h->mirror_valid = false; // (whatever ran wrote the columns; only k_tick_mirror leaves a plane that describes them)
+    const bool mirror_ran = plan.mirror && e == hipSuccess;
+    h->mirror_valid = false; // (whatever ran wrote the columns; only the mirror kernels leave a plane that describes them)
     if (e != hipSuccess) return rg_fail(RG_ERR_NO_DEVICE, send ? "tick + send stage launch failed: %s" : "tick launch failed: %s", hipGetErrorString(e));
-    if (plan.mirror) {
+    if (mirror_ran) {
         h->mirror_valid = true;
-        (plan.mirror == 2u ? h->mirror_packed : h->mirror_build)++;
+        (plan.mirror != (u32)RG_MK_BUILD ? h->mirror_packed : h->mirror_build)++;
         h->mirror_win_launches++;
     }
     if (rode) h->pub_tick_evt = evt_slot;
@@ -375,6 +418,10 @@ static int rg_fused_run(rg_engine *h, const rg_msgs *m, u32 t0, u32 n, uint32_t 
     fm.out_t = dev_out_t + (size_t)t0 * h->G;
     fm.commit_t = dev_commit_t ? (u64 *)dev_commit_t + (size_t)t0 * h->G : nullptr;
     fm.n_ticks = n;
+    // (log-term ticks of this call run as single ticks between the fused launches, on the mirror kernels where the plan allows:
+    // a run of them can leave the two columns behind the plane, and k_tick_fused loads and stores the columns -- settled first)
+    const int src = rg_mirror_settle(h, RG_MC_TICK_OTHER);
+    if (src) return src;
     h->launch->fused(h->stream, h->st, fm, h->any_group_commit);
     h->mirror_valid = false; // (a log-term tick of this call may have run as k_tick_mirror before this launch: the columns move on without the plane)
     hipError_t e = hipGetLastError();

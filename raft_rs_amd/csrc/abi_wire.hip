@@ -64,6 +64,8 @@ extern "C" int rg_workload_gen(rg_engine *h, const rg_workload *w, uint64_t firs
                                uint64_t *mc, uint64_t *mh, uint64_t *mrs, uint8_t *mf) try {
     if (!h || !w || !mi || !mc || !mh || !mrs || !mf) return rg_fail(RG_ERR_INVALID_ARG, "rg_workload_gen: bad argument");
     RG_ENTER_KEEP(h); // (k_wl_gen reads the state and writes the caller's message buffers only: the read mirror stays)
+    const int src = rg_mirror_settle(h, RG_MC_KEEP_LOOK); // (... st.match among it: current before the generator looks)
+    if (src) return src;
     hipLaunchKernelGGL(k_wl_gen, dim3(rg_grid(h->G, RG_BLOCK)), dim3(RG_BLOCK), 0, h->stream, h->st, (u64)w->seed,
                        w->workload | (w->reserved << 8), h->P, (u64)first, (u64)tick, (u64 *)mi, (u64 *)mc, (u64 *)mh, (u64 *)mrs, mf);
     hipError_t e = hipGetLastError();

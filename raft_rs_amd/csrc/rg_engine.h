@@ -59,6 +59,9 @@
 struct rg_engine;
 int rg_mailbox_quiesce(rg_engine *h);            // abi_mirror.hip
 int rg_require_hints_resolved(rg_engine *h, const char *who); // abi_tick.hip
+// abi_tick.hip: one step of the read mirror's host state (rg_mirror_host.h) for a call of class `call` that launches no mirror
+// kernel itself; where the step asks for it, the settle kernel goes onto the engine's stream. -> RG_OK or the launch's error
+int rg_mirror_settle(rg_engine *h, RgMirrorCall call);
 // Every entry point that puts work on the engine's stream starts here: select the device and, if the resident mailbox
 // kernel is on the stream (rg_mailbox_start), tell it to leave -- stream order would make the call wait for it anyway
 // (until its idle timeout), this makes the wait a few microseconds.
@@ -66,13 +69,22 @@ int rg_require_hints_resolved(rg_engine *h, const char *who); // abi_tick.hip
 // dense tick rebuilds the plane from the columns. Dropping is always right; the few entry points that are KNOWN to write none of
 // RG_COL_MATCH / RG_COL_PR_COMMIT / RG_COL_COMMIT -- the dense tick itself, rg_results, rg_result_counts, rg_sync, rg_msg_stats,
 // rg_read_column, the workload generator -- enter through RG_ENTER_KEEP / RG_ENTER_STEP_KEEP, which put the flag back.
-#define RG_ENTER(h)                                                                                \
+#define RG_ENTER_BASE(h)                                                                           \
     do {                                                                                           \
         (h)->mirror_valid = false;                                                                 \
         (h)->pub_tick_evt = -1; /* (whatever this call enqueues comes behind the last tick's event) */ \
         RG_HIP(hipSetDevice((h)->cfg.device));                                                     \
         int rc__ = rg_mailbox_quiesce(h);                                                          \
         if (rc__) return rc__;                                                                     \
+    } while (0)
+// ... behind the SETTLE: where write-behind launches left the two columns behind the plane (rg_engine::cols_behind, rg_mirror.h),
+// they are written back before the call does anything else -- on the stream the engine has at that moment -- and the packed
+// streak ends (rg_mirror_host.h: RG_MC_DROP).
+#define RG_ENTER(h)                                                                                \
+    do {                                                                                           \
+        const int src__ = rg_mirror_settle(h, RG_MC_DROP);                                         \
+        if (src__) return src__;                                                                   \
+        RG_ENTER_BASE(h);                                                                          \
     } while (0)
 // ... and the entry points that start the NEXT step (device Inflights: nothing of it is enqueued while a host hint of the last
 // one is unanswered)
@@ -82,17 +94,20 @@ int rg_require_hints_resolved(rg_engine *h, const char *who); // abi_tick.hip
         const int hrc__ = rg_require_hints_resolved(h, who);                                       \
         if (hrc__) return hrc__;                                                                   \
     } while (0)
-// (a failed entry leaves the mirror dropped)
+// (a failed entry leaves the mirror dropped; the KEEP forms neither settle nor end a write-behind streak -- a KEEP call that
+// reads match or committed_index settles by itself, rg_mirror_settle(h, RG_MC_KEEP_LOOK))
 #define RG_ENTER_KEEP(h)                                                                           \
     do {                                                                                           \
         const bool mv__ = (h)->mirror_valid;                                                       \
-        RG_ENTER(h);                                                                               \
+        RG_ENTER_BASE(h);                                                                          \
         (h)->mirror_valid = mv__;                                                                  \
     } while (0)
 #define RG_ENTER_STEP_KEEP(h, who)                                                                 \
     do {                                                                                           \
         const bool mv__ = (h)->mirror_valid;                                                       \
-        RG_ENTER_STEP(h, who);                                                                     \
+        RG_ENTER_BASE(h);                                                                          \
+        const int hrc__ = rg_require_hints_resolved(h, who);                                       \
+        if (hrc__) return hrc__;                                                                   \
         (h)->mirror_valid = mv__;                                                                  \
     } while (0)
 
@@ -313,6 +328,9 @@ struct rg_engine {
                         // cell offsets, device Inflights, RG_CFGF_NO_READ_MIRROR)
     bool mirror_valid;  // the plane describes RG_COL_MATCH / RG_COL_PR_COMMIT / RG_COL_COMMIT as they stand: set by the dense tick
                         // that wrote it, cleared by every other entry (RG_ENTER)
+    bool cols_behind;   // write-behind launches have run since the last settle: in the blocks whose words hold no escape the plane IS
+                        // the state and the two columns are stale (rg_mirror_host.h: RgMirrorHost::behind)
+    u32 mirror_streak;  // packed write-through launches since the last build launch or settle point (RgMirrorHost::streak)
     bool mirror_off;    // for good: somebody can write those columns without an entry point -- rg_column_ptr handed one of them out,
                         // or a tick was captured into a graph, which replays it behind the engine's back
     // escapes, watched without a synchronisation (rg_mirror.h: RgMirrorEsc): the device's running count of waves that stored an

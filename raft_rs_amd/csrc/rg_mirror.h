@@ -3,10 +3,14 @@
 // five slots). Included by rg_tick_kernels.h behind rg_load_group / rg_store_group; the host twin of the tests
 // (tests/host_check/mirror_twin.hip) compiles the same functions for the CPU.
 //
-// The mirror is a CACHE of the two u64 columns, never their replacement: the columns are stored exactly as before and are
-// correct after every launch; only k_tick_mirror writes the plane and only k_tick_mirror reads it. The one protocol is
-// invalidation, on the host (rg_engine::mirror_valid, cleared by RG_ENTER): a tick that finds the plane invalid loads the
-// columns as rg_load_group does ("build"), a tick that finds it valid loads the words ("packed"); both leave a valid plane.
+// The mirror starts as a CACHE of the two u64 columns: k_tick_mirror stores them exactly as before and they are correct after
+// every such launch; only the mirror kernels write the plane and only they read it. The first protocol is invalidation, on the
+// host (rg_engine::mirror_valid, cleared by RG_ENTER): a tick that finds the plane invalid loads the columns as rg_load_group
+// does ("build"), a tick that finds it valid loads the words ("packed"); both leave a valid plane.
+// Once packed launches follow one another (RG_MIRROR_WB_AFTER of them, rg_mirror_host.h) the plane becomes the STATE of those
+// two columns: k_tick_mirror_wb stores the words and no longer the cells ("write-behind", below), the host remembers that the
+// columns are behind (rg_engine::cols_behind), and every entry that reads or writes them, or ends the streak, first writes them
+// back from the plane (rg_mirror_settle). The columns are then what a write-through engine would hold, bit for bit.
 //
 // The word of slot p, with c = the group's commit index as the tick leaves it (RgGroup::commit at store time, which is what
 // the next tick loads from RG_COL_COMMIT):
@@ -22,6 +26,7 @@
 // a slot WITHOUT one gets the word 0 (rg_store_mirror), which decodes to values no tick looks at. So rg_group_tick sees the
 // operands rg_load_group would have produced wherever it reads them, and rg_store_group stores what it would have stored.
 #pragma once
+#include "rg_mirror_host.h" // RG_MIRROR_WB_AFTER, RgMirrorKernel: the host's side
 
 #define RG_MIRROR_MT_ESC 0x8000u
 #define RG_MIRROR_PC_ESC 0xffffu
@@ -110,6 +115,64 @@ template <int P, typename IX> RG_HD bool rg_store_mirror(const RgGroup<P> &r, u3
         rg_at(pk, (IX)p * (IX)stride + g) = w;
     }
     return esc;
+}
+
+// ---- write-behind (k_tick_mirror_wb) -------------------------------------------------------------------------------------------
+// While packed launches follow one another nothing reads the two u64 columns: the next tick reads the words. The write-behind
+// store therefore leaves the match / committed_index cells alone and stores the words only -- per WAVE (a block of 64 consecutive
+// groups), under one invariant:
+//   no word of the block holds an escape  ->  the words are the state; the block's cells may be stale
+//   some word of the block holds one      ->  the block's cells are current
+// The wave ballots the escapes of the words it is about to store. A wave with one stores EVERY match / committed_index cell of
+// its slots that have a Progress, from the registers (so the loader's wave-uniform escape branch, which re-reads all 2 P cells of
+// every lane, finds what the columns of a write-through engine would hold); a wave without one stores none. The cells of a slot
+// WITHOUT a Progress are never stored -- as rg_store_group leaves them (no event is applied to such a slot, so it has no dirty
+// bit; RG_OPT_WAVE_ST, which would widen a neighbour's store over them, switches write-behind off: rg_tick_kernels.h).
+// -> does any field of this group hold an escape
+template <int P, typename IX> RG_HD bool rg_store_mirror_wb(const RgGroup<P> &r, const RgState &st, u32 *pk, IX g) {
+    const u32 present = RG_CFG_PRESENT(r.cfg);
+    u32 w[P];
+    bool esc = false;
+#pragma unroll
+    for (int p = 0; p < P; p++) {
+        w[p] = ((present >> p) & 1u) ? rg_mirror_encode(r.mt[p], r.pc[p], r.commit) : 0u;
+        esc = esc || (w[p] & 0xffffu) == RG_MIRROR_MT_ESC || (w[p] >> 16) == RG_MIRROR_PC_ESC;
+    }
+    if (__builtin_expect(rg_mirror_any(esc), 0)) {
+        typedef typename std::conditional<std::is_same<IX, u32>::value, rg_u32o, IX>::type IXO;
+#pragma unroll
+        for (int p = 0; p < P; p++) {
+            if (!((present >> p) & 1u)) continue;
+            const IXO o = (IXO)(u64)((IX)p * (IX)st.stride + g);
+            rg_at(st.match, o) = r.mt[p];
+            rg_at(st.prc, o) = r.pc[p];
+        }
+    }
+#pragma unroll
+    for (int p = 0; p < P; p++) rg_at(pk, (IX)p * (IX)st.stride + g) = w[p];
+    return esc;
+}
+
+// The settle (k_mirror_settle, rg_mirror_settle): the two columns written from the plane, once, when something is about to look
+// at them or to write them. One lane per group, one wave per block of 64 groups: a block whose words hold an escape is left
+// alone (its cells are current, and an escaped field cannot be decoded); in every other block each slot the cfg word names as
+// present gets match = decode(word, commit) and committed_index = decode(word, commit). Nothing else is touched.
+RG_HD void rg_mirror_settle_group(const RgState &st, const u32 *pk, u32 P, u64 g) {
+    bool esc = false;
+    for (u32 p = 0; p < P; p++) {
+        const u32 w = pk[(u64)p * st.stride + g];
+        esc = esc || (w & 0xffffu) == RG_MIRROR_MT_ESC || (w >> 16) == RG_MIRROR_PC_ESC;
+    }
+    if (rg_mirror_any(esc)) return;
+    const u64 c = st.commit[g];
+    const u32 present = RG_CFG_PRESENT(st.cfg[g]);
+    for (u32 p = 0; p < P; p++) {
+        if (!((present >> p) & 1u)) continue;
+        const u64 o = (u64)p * st.stride + g;
+        const u32 w = pk[o];
+        st.match[o] = rg_mirror_match(w, c);
+        st.prc[o] = rg_mirror_prc(w, c);
+    }
 }
 
 // What the host learns about escapes without a synchronisation. A wave that stored an escape adds 1 to a count in device memory

@@ -141,7 +141,8 @@ RG_HD void rg_load_group(RgGroup<P> &r, const RgState &st, const RgMsgs &ms, IX 
 // WAVE_ST (kernels whose lanes hold CONSECUTIVE groups, all lanes of the wave arriving here together): RG_OPT_WAVE_ST
 // EARLY: the tick ran with RgEarlyStores -- `next` and the followers' committed_index are in memory already; the one
 // committed_index cell still due is the leader's own (RgGroup::pc_self, which RgTick::self_committed may have raised).
-template <int P, typename IX, int WHICH = 3, bool WAVE_ST = false, bool NTS = false, bool EARLY = false>
+// CELLS = false: everything but the match / committed_index cells (k_tick_mirror_wb: the words stand for them).
+template <int P, typename IX, int WHICH = 3, bool WAVE_ST = false, bool NTS = false, bool EARLY = false, bool CELLS = true>
 RG_HD void rg_store_group(const RgGroup<P> &r, const RgState &st, IX g) {
     u32 d = r.dirty;
 #if RG_OPT_UNCOND_ST
@@ -163,9 +164,9 @@ RG_HD void rg_store_group(const RgGroup<P> &r, const RgState &st, IX g) {
 #pragma unroll
     for (int p = 0; p < P; p++) {
         const IX o = (IX)p * (IX)st.stride + g;
-        if ((WHICH & 1) && (d & (1u << p))) rg_st<(RG_OPT_NT_ALL != 0 || NTS)>(rg_at(st.match, o), r.mt[p]);
+        if (CELLS && (WHICH & 1) && (d & (1u << p))) rg_st<(RG_OPT_NT_ALL != 0 || NTS)>(rg_at(st.match, o), r.mt[p]);
         if (!EARLY && (WHICH & 2) && (d & (1u << (8 + p)))) rg_st<((RG_OPT_NT_ALL | RG_OPT_NT_NEXT) != 0 || NTS)>(rg_at(st.next, o), r.nx[p]);
-        if ((WHICH & 1) && (d & (1u << (16 + p)))) rg_st<(RG_OPT_NT_ALL != 0 || NTS)>(rg_at(st.prc, o), EARLY ? r.pc_self : r.pc[p]);
+        if (CELLS && (WHICH & 1) && (d & (1u << (16 + p)))) rg_st<(RG_OPT_NT_ALL != 0 || NTS)>(rg_at(st.prc, o), EARLY ? r.pc_self : r.pc[p]);
     }
     if ((WHICH & 2) && (d & RG_DIRTY_PF)) rg_at(st.pflags, g) = r.pf;
     if (WHICH & 1) {
@@ -324,6 +325,37 @@ template <int P, typename IX, int NTM, bool PACKED> __global__ RG_LANE_BOUNDS(P)
     rg_group_tick<P, false, RG_LANE_NX, false, IX, ES>(r, a.st, a.ms, g);
     rg_store_group<P, IX, 3, true, false, false>(r, a.st, g);
     rg_mirror_note_escape(rg_store_mirror<P, IX>(r, a.pk, a.st.stride, g), a.esc);
+}
+
+// The packed launch of a STREAK of packed launches (rg_mirror_host.h): loads like k_tick_mirror<.., PACKED>, runs the same tick,
+// stores the group without its match / committed_index cells (CELLS = false) and then the words -- with the cells of a wave
+// that stores an escape (rg_store_mirror_wb). The launch's first lane marks the word behind the escape count (one plain vector
+// store per launch): "the columns are behind the plane", which is what lets the settle kernel sit in a captured graph.
+#define RG_MIRROR_BEHIND_WORD 16u /* u32 index from RgMirrorEsc::count: a cache line of its own */
+// (RG_OPT_WAVE_ST, an experiment, rewrites the cells of slots without a Progress, which the settle could not reproduce: with it
+// write-behind never engages)
+#define RG_MIRROR_WB_AFTER_EFFECTIVE (RG_OPT_WAVE_ST ? 0u : (unsigned)RG_MIRROR_WB_AFTER)
+template <int P, typename IX, int NTM> __global__ RG_LANE_BOUNDS(P) void k_tick_mirror_wb(RgMirrorArgs a) {
+    static_assert(NTM == 0 || NTM == 1, "the cached regimes only, as k_tick_mirror");
+    typedef typename RgLaneStores<P, false, NTM != 0 || (RG_OPT_NT_MSG != 0)>::type ES;
+    static_assert(!ES::on && !ES::late_pc, "the mirror is encoded from pc[] / mt[] at the end of the tick: no early stores, no late loads");
+    const u64 g64 = (u64)blockIdx.x * RG_BLOCK + threadIdx.x;
+    if (g64 >= a.st.G) return;
+    const IX g = (IX)g64;
+    RgGroup<P> r;
+    rg_load_group_pk<P, IX, NTM != 0 || (RG_OPT_NT_MSG != 0)>(r, a.st, a.ms, a.pk, g);
+    rg_group_tick<P, false, RG_LANE_NX, false, IX, ES>(r, a.st, a.ms, g);
+    rg_store_group<P, IX, 3, true, false, false, false>(r, a.st, g);
+    rg_mirror_note_escape(rg_store_mirror_wb<P, IX>(r, a.st, a.pk, g), a.esc);
+    if (g64 == 0) a.esc.count[RG_MIRROR_BEHIND_WORD] = 1u;
+}
+// (the settle kernel: rg_mirror_settle_group for one group per lane, a wave per block of 64 groups; every block returns at once
+// when the launches in front of it left the columns current -- the word is clear -- so a captured settle replays as a no-op)
+template <int P> __global__ __launch_bounds__(64) void k_mirror_settle(RgState st, const u32 *pk, const u32 *behind) {
+    if (*behind == 0) return;
+    const u64 g = (u64)blockIdx.x * 64 + threadIdx.x;
+    if (g >= st.G) return;
+    rg_mirror_settle_group(st, pk, (u32)P, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1275,8 +1307,10 @@ struct RgTickLaunch {
     void (*mailbox)(hipStream_t stream, const RgState &st, const RgMsgs &ms, bool gc, const RgIngest &a0, u32 *ctr_base, u64 *rh,
                     u64 *mflags_rw, const RgListOut &lo, RgMbox *mb, u64 idle_ticks, u64 max_ticks, const RgSmallSend &ss0);
     // the lane kernel with the read mirror (k_tick_mirror: no group commit, 32-bit cell offsets, ntm 0 or 1: the caller checks all
-    // three); packed = the plane is valid and is read in the place of the match / committed_index columns
-    bool (*mirror)(hipStream_t stream, const RgState &st, const RgMsgs &ms, int ntm, u32 *pk, const RgMirrorEsc &esc, bool packed, hipEvent_t stop_evt);
+    // three). mode (RgMirrorKernel, rg_mirror_host.h): RG_MK_BUILD = the plane is built from the columns, RG_MK_PACKED = it is valid and
+    // read in the place of the match / committed_index columns, RG_MK_PACKED_WB = the same and the two columns are no longer stored
+    // (k_tick_mirror_wb); RG_MK_NONE = no tick at all: the settle kernel (k_mirror_settle; ms, ntm and stop_evt are not looked at)
+    bool (*mirror)(hipStream_t stream, const RgState &st, const RgMsgs &ms, int ntm, u32 *pk, const RgMirrorEsc &esc, int mode, hipEvent_t stop_evt);
 };
 template <int P> const RgTickLaunch &rg_tick_launch_p(); // (tick_inst.hip, -DRG_P=P)
 const RgTickLaunch &rg_tick_launch(u32 P);                // (abi_state.hip)
@@ -1361,15 +1395,23 @@ template <int P> bool rg_launch_tick_split_t(hipStream_t stream, const RgState &
     RG_LAUNCH_TICK((k_tick_split<P, typename RgLaneIx<P>::type>), dim3(rg_grid_for(st.G, RG_BLOCK)), dim3(RG_BLOCK), stream, stop_evt, a);
     return stop_evt != nullptr;
 }
-template <int P> bool rg_launch_tick_mirror_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, int ntm, u32 *pk, const RgMirrorEsc &esc, bool packed, hipEvent_t stop_evt) {
+template <int P> bool rg_launch_tick_mirror_t(hipStream_t stream, const RgState &st, const RgMsgs &ms, int ntm, u32 *pk, const RgMirrorEsc &esc, int mode, hipEvent_t stop_evt) {
     const dim3 grid(rg_grid_for(st.G, RG_BLOCK)), block(RG_BLOCK);
+    if (mode == RG_MK_NONE) {
+        hipLaunchKernelGGL((k_mirror_settle<P>), dim3(rg_grid_for(st.G, 64)), dim3(64), 0, stream, st, (const u32 *)pk, (const u32 *)(esc.count + RG_MIRROR_BEHIND_WORD));
+        return false;
+    }
+    const bool packed = mode != RG_MK_BUILD;
     RgMirrorArgs a;
     a.st = st;
     a.ms = ms;
     a.pk = pk;
     a.esc = esc;
     typedef typename RgLaneIx<P>::type IXP;
-    if (ntm) {
+    if (mode == RG_MK_PACKED_WB) {
+        if (ntm) RG_LAUNCH_TICK((k_tick_mirror_wb<P, IXP, 1>), grid, block, stream, stop_evt, a);
+        else RG_LAUNCH_TICK((k_tick_mirror_wb<P, IXP, 0>), grid, block, stream, stop_evt, a);
+    } else if (ntm) {
         if (packed) RG_LAUNCH_TICK((k_tick_mirror<P, IXP, 1, true>), grid, block, stream, stop_evt, a);
         else RG_LAUNCH_TICK((k_tick_mirror<P, IXP, 1, false>), grid, block, stream, stop_evt, a);
     } else {
